@@ -11,6 +11,13 @@ Launch (driver contract):
   python bench.py --gpus 1 --steps K --warmup W
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
       --master-addr 127.0.0.1 bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the result line.
+  --full              also times the whole-job fit() (host->device ingest +
+                      init + 30 Lloyd iterations) and reports `fit_wall_s`,
+                      `fit_rows_per_s` and the whole-job `vs_baseline`
+  --dump-outputs DIR  write what the last timed step returned (centers,
+                      labels, counts, inertia) as DIR/<name>.npy
 """
 
 from __future__ import annotations
@@ -39,7 +46,13 @@ def main() -> None:
     ap.add_argument("--rows", type=int, default=None, help="rows per GPU")
     ap.add_argument("--cols", type=int, default=3000)
     ap.add_argument("--k", type=int, default=1000)
+    ap.add_argument("--full", action="store_true",
+                    help="also time the whole-job fit() against the reference's 82 s")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     from spark_rapids_ml_amd.parallel.context import get_comm, init_comm, shutdown_comm
     from spark_rapids_ml_amd.ops import kmeans_assign_reduce
@@ -68,6 +81,8 @@ def main() -> None:
     g0.manual_seed(42)
     C = torch.randn(k, cols, generator=g0, device=dev, dtype=torch.float32)
 
+    last = {}  # what the most recent step handed back (for --dump-outputs)
+
     def lloyd_step(C: torch.Tensor) -> torch.Tensor:
         labels, sums, counts, inertia = kmeans_assign_reduce(X, C, x_sq)
         buf = torch.empty((k, cols + 2), dtype=torch.float64, device=sums.device)
@@ -79,6 +94,7 @@ def main() -> None:
         nonempty = g_counts > 0
         C_new = C.clone()
         C_new[nonempty] = (buf[nonempty, :cols] / g_counts[nonempty, None]).to(C.dtype)
+        last.update(labels=labels, counts=g_counts, inertia=buf[0, cols + 1])
         return C_new
 
     for _ in range(args.warmup):
@@ -101,25 +117,47 @@ def main() -> None:
     value = total_rows * args.steps / elapsed
     ms_per_step = elapsed / args.steps * 1000.0
 
-    # Whole-job fit wall-clock (the honest vs-baseline basis):
-    # host→device ingest + k init + 30 Lloyd iterations through the real
-    # estimator path, exactly the job the reference's 82 s covers.
-    from spark_rapids_ml_amd import KMeans as _KMeans
-    from spark_rapids_ml_amd.data import DataFrame as _DF
+    if args.dump_outputs and comm.rank == 0:
+        # 1000×3000 f32 centers + 1M labels ≈ 16 MB at the default shape
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, t, dt in (
+            ("centers", C, np.float32),
+            ("labels", last["labels"], np.float32),  # ids < k: exact in f32
+            ("counts", last["counts"], np.float64),
+            ("inertia", last["inertia"].reshape(1), np.float64),
+        ):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"),
+                    t.detach().cpu().numpy().astype(dt))
 
-    Xh = X.cpu().numpy()
-    del X, x_sq
-    if on_gpu:
-        torch.cuda.empty_cache()
     fit_iters = 30 if on_gpu else 5
-    comm.barrier()
-    t0 = time.perf_counter()
-    _KMeans(k=k, maxIter=fit_iters, initMode="random", seed=5).fit(_DF.from_numpy(Xh))
-    if on_gpu:
-        torch.cuda.synchronize(dev)
-    comm.barrier()
-    fit_wall_s = comm.allreduce_scalar(time.perf_counter() - t0, "max")
-    fit_rows_per_s = total_rows * fit_iters / fit_wall_s
+    full = {}
+    if args.full:
+        # Whole-job fit wall-clock (the honest vs-baseline basis):
+        # host→device ingest + k init + 30 Lloyd iterations through the real
+        # estimator path, exactly the job the reference's 82 s covers.
+        from spark_rapids_ml_amd import KMeans as _KMeans
+        from spark_rapids_ml_amd.data import DataFrame as _DF
+
+        Xh = X.cpu().numpy()
+        del X, x_sq
+        if on_gpu:
+            torch.cuda.empty_cache()
+        comm.barrier()
+        t0 = time.perf_counter()
+        _KMeans(k=k, maxIter=fit_iters, initMode="random", seed=5).fit(_DF.from_numpy(Xh))
+        if on_gpu:
+            torch.cuda.synchronize(dev)
+        comm.barrier()
+        fit_wall_s = comm.allreduce_scalar(time.perf_counter() - t0, "max")
+        fit_rows_per_s = total_rows * fit_iters / fit_wall_s
+        full = {
+            # whole-job ÷ whole-job: full fit() wall-clock (ingest+init+30
+            # Lloyd iters) vs the reference's published 82 s on the same
+            # 1M×3000 k=1000 workload — NOT the steady-state step rate
+            "vs_baseline": fit_rows_per_s / BASELINE_ROWS_PER_S if on_gpu else None,
+            "fit_wall_s": fit_wall_s,
+            "fit_rows_per_s": fit_rows_per_s,
+        }
 
     if comm.rank == 0:
         out = {
@@ -132,12 +170,7 @@ def main() -> None:
             "ms_per_step": ms_per_step,
             "higher_is_better": True,
             "scaling": "weak",
-            # whole-job ÷ whole-job: full fit() wall-clock (ingest+init+30
-            # Lloyd iters) vs the reference's published 82 s on the same
-            # 1M×3000 k=1000 workload — NOT the steady-state step rate
-            "vs_baseline": fit_rows_per_s / BASELINE_ROWS_PER_S if on_gpu else None,
-            "fit_wall_s": fit_wall_s,
-            "fit_rows_per_s": fit_rows_per_s,
+            **full,
             "steady_state_vs_baseline": value / BASELINE_ROWS_PER_S if on_gpu else None,
             "dtype": "fp32",
             "data": "synthetic",

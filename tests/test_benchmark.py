@@ -80,6 +80,42 @@ def test_gen_data_cli(tmp_path):
     assert df.num_rows == 500
 
 
+def _run_flagship(*extra):
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run(
+        [sys.executable, "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1",
+         "--rows", "3000", "--cols", "64", "--k", "16", *extra],
+        capture_output=True, text=True, cwd=repo, timeout=300,
+    )
+    assert out.returncode == 0, out.stderr
+    return json.loads(out.stdout.strip().splitlines()[-1])
+
+
+def test_flagship_plain_run_and_dump(tmp_path):
+    """A plain run reports the step figures only and --dump-outputs writes
+    the last step's arrays; --full adds the whole-job fit figures."""
+    dump = tmp_path / "dump"
+    rep = _run_flagship("--dump-outputs", str(dump))
+    assert rep["metric"] == "kmeans_fit_rows_per_s" and rep["higher_is_better"] is True
+    assert rep["steps"] == 2 and rep["dtype"] == "fp32"
+    assert rep["ms_per_step"] > 0
+    assert rep["value"] == pytest.approx(3000 * 1000.0 / rep["ms_per_step"])
+    assert "fit_wall_s" not in rep and "vs_baseline" not in rep
+    centers = np.load(dump / "centers.npy")
+    labels = np.load(dump / "labels.npy")
+    counts = np.load(dump / "counts.npy")
+    inertia = np.load(dump / "inertia.npy")
+    assert centers.shape == (16, 64) and centers.dtype == np.float32
+    assert labels.shape == (3000,) and labels.dtype == np.float32
+    assert counts.dtype == np.float64 and inertia.dtype == np.float64
+    assert counts.sum() == 3000 and inertia.shape == (1,) and inertia[0] > 0
+    np.testing.assert_array_equal(np.bincount(labels.astype(np.int64), minlength=16), counts)
+
+    full = _run_flagship("--full")
+    assert full["fit_wall_s"] > 0 and full["fit_rows_per_s"] > 0
+    assert "vs_baseline" in full and full["ms_per_step"] > 0
+
+
 def test_gen_classification_redundant_and_clusters():
     X, y = gen_data.gen_classification(
         3000, 20, n_classes=2, n_informative=6, n_redundant=4,

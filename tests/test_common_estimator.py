@@ -73,7 +73,8 @@ class DummyEstimator(_DummyParams, Estimator):
         self.seen["params"] = dict(params)
         self.seen["pdesc_m"] = ctx.pdesc.m
         self.seen["pdesc_parts"] = list(ctx.pdesc.parts_rank_size)
-        buf = torch.cat([Xt.sum(dim=0), torch.tensor([float(Xt.shape[0])], dtype=Xt.dtype)])
+        n_rows = torch.tensor([float(Xt.shape[0])], dtype=Xt.dtype, device=Xt.device)
+        buf = torch.cat([Xt.sum(dim=0), n_rows])
         buf = ctx.comm.allreduce_t(buf)
         mean = (buf[:-1] / buf[-1]).cpu().numpy()
         return {"mean_": mean * float(params["alpha"])}
