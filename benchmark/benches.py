@@ -201,12 +201,14 @@ class BenchApproximateNearestNeighbors(BenchNearestNeighbors):
         ap.add_argument("--algorithm", default="ivfflat")
         ap.add_argument("--nlist", type=int, default=256)
         ap.add_argument("--nprobe", type=int, default=32)
+        ap.add_argument("--metric", default="euclidean")
 
     def make_estimator(self, args):
         return ApproximateNearestNeighbors(
             k=args.k,
             algorithm=args.algorithm,
             algoParams={"nlist": args.nlist, "nprobe": args.nprobe},
+            metric=args.metric,
         )
 
 

@@ -2408,6 +2408,105 @@ __global__ __launch_bounds__(256) void gather_dists_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// ivf_scan_topk: fused IVF-Flat probed-list scan. One wave per (query, probed
+// list) pair: the query row is staged in registers as gather_dists stages A,
+// the list's rows (contiguous in the list-sorted item copy) are read
+// coalesced and reduced by the 6-step butterfly, and the wave keeps the k
+// best in the 64-slot running top-k of knn_merge_topk (lane = slot, tau =
+// worst kept key). The key is wave-uniform after the butterfly, so the insert
+// test is a uniform branch; only the owner-of-tau ballot remains. No distance
+// block is ever materialized. Key, smaller is better:
+//   MODE 0: sum (q-x)^2 in the difference form    MODE 1: -q.x
+// NSEG (elements per lane, d <= 64*NSEG) is a template parameter so the
+// query registers are statically indexed; ROWS list rows are in flight per
+// wave before their butterflies to overlap the load latency.
+// Reference: cuVS ivf_flat search (knn.py:1485-1491).
+// ---------------------------------------------------------------------------
+
+template <int NSEG, int MODE>
+__global__ __launch_bounds__(256) void ivf_scan_topk_kernel(
+    const float* __restrict__ Q,          // [nq, d]
+    const float* __restrict__ Xs,         // [n, d] rows sorted by list
+    const int64_t* __restrict__ list_off,   // [nlist + 1]
+    const int64_t* __restrict__ pair_q,     // [P]
+    const int64_t* __restrict__ pair_list,  // [P]
+    const int64_t* __restrict__ pair_out,   // [P] output row of each pair
+    int64_t P, int64_t nq, int64_t n, int64_t nlist, int64_t n_out, int d, int k,
+    float* __restrict__ part_key,         // [n_out, 64]
+    int64_t* __restrict__ part_pos) {     // [n_out, 64] positions into Xs
+  constexpr int ROWS = NSEG <= 4 ? 4 : (NSEG <= 16 ? 2 : 1);
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int64_t p = (int64_t)blockIdx.x * 4 + wave;
+  if (p >= P) return;
+  const int64_t qi = pair_q[p];
+  const int64_t li = pair_list[p];
+  const int64_t oi = pair_out[p];
+  // a malformed work item is dropped, never dereferenced (wave-uniform)
+  if (qi < 0 || qi >= nq || li < 0 || li >= nlist || oi < 0 || oi >= n_out) return;
+  int64_t lo = list_off[li], hi = list_off[li + 1];
+  lo = lo < 0 ? 0 : lo;
+  hi = hi > n ? n : hi;
+
+  float q_reg[NSEG];
+  const float* qrow = Q + qi * d;
+#pragma unroll
+  for (int s = 0; s < NSEG; ++s) {
+    const int idx = s * 64 + lane;
+    q_reg[s] = (idx < d) ? qrow[idx] : 0.0f;
+  }
+
+  // lanes >= k are dead slots (-inf never owns tau); live slots start empty
+  float cur_k = lane < k ? INFINITY : -INFINITY;
+  int64_t cur_p = -1;
+  float tau = INFINITY;
+
+  for (int64_t j0 = lo; j0 < hi; j0 += ROWS) {
+    float acc[ROWS];
+#pragma unroll
+    for (int u = 0; u < ROWS; ++u) {
+      acc[u] = 0.0f;
+      if (j0 + u < hi) {  // wave-uniform
+        const float* xrow = Xs + (j0 + u) * d;
+#pragma unroll
+        for (int s = 0; s < NSEG; ++s) {
+          const int idx = s * 64 + lane;
+          const float xv = (idx < d) ? xrow[idx] : 0.0f;
+          if (MODE == 0) {
+            const float diff = q_reg[s] - xv;
+            acc[u] = fmaf(diff, diff, acc[u]);
+          } else {
+            acc[u] = fmaf(q_reg[s], xv, acc[u]);
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < ROWS; ++u) {
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) acc[u] += __shfl_xor(acc[u], off, 64);
+    }
+#pragma unroll
+    for (int u = 0; u < ROWS; ++u) {
+      // every lane holds the same sum after the butterfly; reading it from
+      // the first lane lets the compiler see the insert test as uniform
+      const float key = __int_as_float(__builtin_amdgcn_readfirstlane(
+          __float_as_int(MODE == 0 ? acc[u] : -acc[u])));
+      if (j0 + u < hi && key < tau) {  // no candidate ballot needed
+        const unsigned long long owners = __ballot(cur_k == tau);
+        const int owner = __ffsll((unsigned long long)owners) - 1;
+        if (lane == owner) { cur_k = key; cur_p = j0 + u; }
+        tau = __int_as_float(__builtin_amdgcn_readfirstlane(
+            __float_as_int(wave_max_f32(cur_k))));
+      }
+    }
+  }
+
+  part_key[oi * 64 + lane] = cur_k;
+  part_pos[oi * 64 + lane] = cur_p;
+}
+
+// ---------------------------------------------------------------------------
 // CSR GLM kernels (the reference's LogisticRegressionMG sparse path,
 // classification.py:960-966, runs cuML SpMM; torch/rocSPARSE here spent its
 // time in f64 index_add column stats, a 400M-pair radix-sort transpose and
@@ -3063,6 +3162,66 @@ torch::Tensor gather_dists(torch::Tensor A, torch::Tensor B, torch::Tensor cand)
   return out;
 }
 
+template <int NSEG>
+static void ivf_scan_topk_launch(int64_t mode, unsigned grid, const float* Q,
+                                 const float* Xs, const int64_t* list_off,
+                                 const int64_t* pair_q, const int64_t* pair_list,
+                                 const int64_t* pair_out, int64_t P, int64_t nq,
+                                 int64_t n, int64_t nlist, int64_t n_out, int d,
+                                 int k, float* part_key, int64_t* part_pos) {
+  if (mode == 0)
+    hipLaunchKernelGGL((ivf_scan_topk_kernel<NSEG, 0>), dim3(grid), dim3(256), 0,
+                       cur_stream(), Q, Xs, list_off, pair_q, pair_list, pair_out,
+                       P, nq, n, nlist, n_out, d, k, part_key, part_pos);
+  else
+    hipLaunchKernelGGL((ivf_scan_topk_kernel<NSEG, 1>), dim3(grid), dim3(256), 0,
+                       cur_stream(), Q, Xs, list_off, pair_q, pair_list, pair_out,
+                       P, nq, n, nlist, n_out, d, k, part_key, part_pos);
+}
+
+std::vector<torch::Tensor> ivf_scan_topk(torch::Tensor Q, torch::Tensor Xs,
+                                         torch::Tensor list_off, torch::Tensor pair_q,
+                                         torch::Tensor pair_list, torch::Tensor pair_out,
+                                         int64_t n_out, int64_t k, int64_t mode) {
+  TORCH_CHECK(Q.is_cuda() && Q.dtype() == torch::kFloat32 && Q.is_contiguous());
+  TORCH_CHECK(Xs.is_cuda() && Xs.dtype() == torch::kFloat32 && Xs.is_contiguous());
+  TORCH_CHECK(Q.dim() == 2 && Xs.dim() == 2 && Q.size(1) == Xs.size(1));
+  for (const torch::Tensor* t : {&list_off, &pair_q, &pair_list, &pair_out})
+    TORCH_CHECK(t->is_cuda() && t->dtype() == torch::kInt64 && t->is_contiguous() &&
+                t->dim() == 1);
+  const int64_t P = pair_q.size(0);
+  TORCH_CHECK(pair_list.size(0) == P && pair_out.size(0) == P);
+  TORCH_CHECK(list_off.size(0) >= 1);
+  TORCH_CHECK(k >= 1 && k <= 64, "ivf_scan_topk supports 1 <= k <= 64");
+  TORCH_CHECK(mode == 0 || mode == 1, "mode must be 0 (L2) or 1 (dot)");
+  TORCH_CHECK(n_out >= 0);
+  const int d = (int)Q.size(1);
+  TORCH_CHECK(d >= 1 && d <= GD_DMAX, "ivf_scan_topk supports d <= 2048");
+  const int64_t nq = Q.size(0), n = Xs.size(0), nlist = list_off.size(0) - 1;
+  auto part_key = torch::full({n_out, 64}, INFINITY, Q.options());
+  auto part_pos = torch::full({n_out, 64}, (int64_t)-1,
+                              Q.options().dtype(torch::kInt64));
+  if (P > 0 && n_out > 0) {
+    TORCH_CHECK((P + 3) / 4 <= 0x7fffffffLL, "too many (query, list) pairs");
+    const unsigned grid = (unsigned)((P + 3) / 4);
+    const int nseg = (d + 63) >> 6;
+#define IVF_SCAN_ARGS                                                             \
+  mode, grid, Q.data_ptr<float>(), Xs.data_ptr<float>(),                          \
+      list_off.data_ptr<int64_t>(), pair_q.data_ptr<int64_t>(),                   \
+      pair_list.data_ptr<int64_t>(), pair_out.data_ptr<int64_t>(), P, nq, n,      \
+      nlist, n_out, d, (int)k, part_key.data_ptr<float>(),                        \
+      part_pos.data_ptr<int64_t>()
+    if (nseg <= 1) ivf_scan_topk_launch<1>(IVF_SCAN_ARGS);
+    else if (nseg <= 2) ivf_scan_topk_launch<2>(IVF_SCAN_ARGS);
+    else if (nseg <= 4) ivf_scan_topk_launch<4>(IVF_SCAN_ARGS);
+    else if (nseg <= 8) ivf_scan_topk_launch<8>(IVF_SCAN_ARGS);
+    else if (nseg <= 16) ivf_scan_topk_launch<16>(IVF_SCAN_ARGS);
+    else ivf_scan_topk_launch<32>(IVF_SCAN_ARGS);
+#undef IVF_SCAN_ARGS
+  }
+  return {part_key, part_pos};
+}
+
 torch::Tensor fil_predict(torch::Tensor X, torch::Tensor feat, torch::Tensor thr,
                           torch::Tensor left, torch::Tensor right, torch::Tensor value,
                           torch::Tensor roots, bool classif) {
@@ -3177,5 +3336,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rf_reroute", &rf_reroute, "one-pass row-to-child reassignment");
   m.def("knn_merge_topk", &knn_merge_topk, "running top-k merge over a GEMM dot block");
   m.def("gather_dists", &gather_dists, "gathered row-vs-candidates squared distances");
+  m.def("ivf_scan_topk", &ivf_scan_topk, "fused IVF-Flat probed-list scan + running top-k");
   m.attr("_is_hip") = true;
 }

@@ -544,7 +544,11 @@ class _DBSCANParams(HasFeaturesCol, HasFeaturesCols, HasPredictionCol, HasIDCol)
     min_samples = Param(
         "dbscan", "min_samples", "core point neighbor threshold.", TypeConverters.toInt
     )
-    metric = Param("dbscan", "metric", "distance metric.", TypeConverters.toString)
+    metric = Param(
+        "dbscan", "metric",
+        "distance metric: euclidean|cosine (reference clustering.py:761); "
+        "cosine rejects zero-norm rows.", TypeConverters.toString,
+    )
     algorithm = Param(
         "dbscan", "algorithm",
         "brute|rbc (reference clustering.py:686-695; rbc is an accelerator "
@@ -812,6 +816,23 @@ class DBSCANModel(_DBSCANParams, Model):
         off = pdesc.row_offset()
         n_local = X_local.shape[0]
         eps2 = eps * eps
+        metric = str(self.getOrDefault("metric") or "euclidean")
+        if metric == "cosine":
+            # on unit rows ||u - v||^2 = 2 (1 - cos), so cosine distance
+            # <= eps is squared L2 <= 2 eps and everything downstream
+            # (dbscan_sweep, the rbc ball cover, the torch path) serves
+            # unchanged. Every rank holds the full Xf: no collective needed.
+            norms = Xf.norm(dim=1, keepdim=True)
+            if n and bool((norms == 0).any()):
+                raise ValueError(
+                    "DBSCAN metric='cosine' is undefined for zero-norm rows"
+                )
+            Xf = Xf / norms
+            eps2 = 2.0 * eps
+        elif metric != "euclidean":
+            raise ValueError(
+                f"unsupported DBSCAN metric {metric!r}; expected euclidean or cosine"
+            )
 
         from ..ops.dispatch import use_hip
 

@@ -13,12 +13,17 @@ Approximate (reference knn.py:838-1723, cuVS): no comms — each rank builds a
 local index over its item shard (IVF-Flat: k-means coarse quantizer reusing
 the KMeans kernels; IVF-PQ: product quantization + exact refine), queries are
 replicated, global top-k merged the same way as exact (reference does it via
-Spark groupBy aggregation, knn.py:1282-1322).
+Spark groupBy aggregation, knn.py:1282-1322). The `metric` param
+(euclidean/l2/sqeuclidean/inner_product/cosine, reference knn.py:1007-1010)
+is carried as a smaller-is-better key through search and merge — see the
+convention table above `_ANN_METRICS`; on the GPU the IVF-Flat probed-list
+scan is the fused `ivf_scan_topk` HIP kernel.
 """
 
 from __future__ import annotations
 
 import math
+import os
 from typing import Any, Dict, Optional, Tuple
 
 import numpy as np
@@ -128,7 +133,11 @@ class _NNModelBase(_NNParams, Model):
         """All-gather per-rank partial top-k (one fused tensor collective —
         the reference moves these with UCX p2p, knn.py:763-774) and merge
         for the local queries. Item ids ride as int32 bit-cast into the
-        float buffer (one collective instead of a pickled-object gather)."""
+        float buffer (one collective instead of a pickled-object gather).
+
+        `my_dists` holds KEYS, smaller is better (for exact kNN the
+        Euclidean distance is its own key); the caller converts the merged
+        keys to the reported distance."""
         import torch as _torch
 
         kp = my_dists.shape[1]
@@ -155,8 +164,13 @@ class _NNModelBase(_NNParams, Model):
         return dl[rows, order], il[rows, order]
 
     def _kneighbors_impl(
-        self, query_df: DataFrame, search_fn
+        self, query_df: DataFrame, search_fn, key_to_dist=None
     ) -> Tuple[DataFrame, DataFrame, DataFrame]:
+        """`search_fn` returns (keys, idx) with smaller keys better and
+        idx -1 for an empty slot; partials are padded with the worst key
+        (+inf), merged on keys, and `key_to_dist` (None: the key is the
+        distance, as for exact Euclidean kNN) maps the merged keys to the
+        reported distances once, at the end."""
         from ..parallel.context import get_comm
 
         comm = get_comm()
@@ -176,7 +190,10 @@ class _NNModelBase(_NNParams, Model):
         q_offset = sum(p.shape[0] for p in q_parts[: comm.rank])
         if X.shape[0] > 0:
             dists, idx = search_fn(Qt, X, k)
-            ids_local = item_ids[as_numpy(idx)]
+            idx_np = as_numpy(idx)
+            ids_local = item_ids[idx_np]
+            if (idx_np < 0).any():  # empty ANN slots keep id -1
+                ids_local = np.where(idx_np >= 0, ids_local, -1)
             d_np = as_numpy(dists)
         else:
             d_np = np.full((Qt.shape[0], k), np.inf, dtype=np.float32)
@@ -190,6 +207,8 @@ class _NNModelBase(_NNParams, Model):
         d_fin, i_fin = self._merge_partials(
             comm, d_np, ids_local, len(query_df), q_offset, k
         )
+        if key_to_dist is not None:
+            d_fin = key_to_dist(d_fin)
         knn_df = DataFrame(
             {
                 f"query_{self.getIdCol()}": qids,
@@ -298,6 +317,51 @@ class NearestNeighborsModel(_NNModelBase):
 # Approximate kNN
 # ---------------------------------------------------------------------------
 
+# Metric convention. Every search function and the partial merge work on a
+# KEY for which smaller is better; the key becomes the reported distance
+# once, after the merge:
+#
+#   metric          preprocessing        key                 reported
+#   euclidean, l2   -                    squared L2          sqrt(key)
+#   sqeuclidean     -                    squared L2          key
+#   cosine          unit-normalise rows  squared L2 of unit  key / 2  (= 1 - cos)
+#   inner_product   -                    -q.x                -key, descending
+#
+# Rows are normalised by max(||.||, 1e-30), so a zero vector stays zero and
+# comes out at cosine distance 0.5 from everything. An empty slot (fewer than
+# k items reachable) has key +inf and id -1: it reports +inf for the ascending
+# metrics and -inf for inner_product.
+_ANN_METRICS = ("euclidean", "l2", "sqeuclidean", "inner_product", "cosine")
+_MODE_L2, _MODE_DOT = 0, 1
+
+
+def _check_metric(value: Any) -> str:
+    if value not in _ANN_METRICS:
+        raise ValueError(
+            f"unsupported metric {value!r}; expected one of {', '.join(_ANN_METRICS)}"
+        )
+    return value
+
+
+def _metric_mode(metric: str) -> int:
+    return _MODE_DOT if metric == "inner_product" else _MODE_L2
+
+
+def _normalize_rows(T: torch.Tensor) -> torch.Tensor:
+    return T / T.norm(dim=1, keepdim=True).clamp_min(1e-30)
+
+
+def _key_to_dist(key: np.ndarray, metric: str) -> np.ndarray:
+    if metric == "inner_product":
+        return -key
+    key = np.maximum(key, 0.0)
+    if metric == "sqeuclidean":
+        return key
+    if metric == "cosine":
+        return key * np.float32(0.5)
+    return np.sqrt(key)
+
+
 
 class _ANNParams(_NNParams):
     algorithm = Param(
@@ -308,7 +372,13 @@ class _ANNParams(_NNParams):
     )
 
     metric = Param(
-        "ann", "metric", "distance metric (euclidean/sqeuclidean).", TypeConverters.toString
+        "ann",
+        "metric",
+        "distance metric: euclidean|l2|sqeuclidean|inner_product|cosine "
+        "(reference knn.py:1007-1010). ivfflat and ivfpq support all five; "
+        "cagra supports euclidean|l2|sqeuclidean. inner_product reports the "
+        "raw dot products, largest first; cosine reports 1 - cos.",
+        TypeConverters.toString,
     )
 
     def __init__(self, **kwargs: Any) -> None:
@@ -316,9 +386,11 @@ class _ANNParams(_NNParams):
         self._setDefault(algorithm="ivfflat", algoParams=None, metric="euclidean")
 
     def setMetric(self, value: str):
-        if value not in ("euclidean", "l2", "sqeuclidean"):
-            raise ValueError("metric must be euclidean/l2/sqeuclidean")
+        _check_metric(value)
         return self._set_params(metric=value)
+
+    def getMetric(self) -> str:
+        return self.getOrDefault("metric")
 
 
 class ApproximateNearestNeighbors(_ANNParams, Estimator):
@@ -380,15 +452,24 @@ class ApproximateNearestNeighborsModel(_ANNModelParams, _NNModelBase):
     def kneighbors(self, query_df: DataFrame) -> Tuple[DataFrame, DataFrame, DataFrame]:
         algo = self.getOrDefault("algorithm").lower()
         algo_params = self.getOrDefault("algoParams") or {}
+        # the constructor sets params without going through setMetric
+        metric = _check_metric(self.getOrDefault("metric"))
         if algo in ("ivfflat", "ivf_flat"):
-            search = self._make_ivfflat_search(algo_params)
+            search = self._make_ivfflat_search(algo_params, metric)
         elif algo in ("ivfpq", "ivf_pq"):
-            search = self._make_ivfpq_search(algo_params)
+            search = self._make_ivfpq_search(algo_params, metric)
         elif algo == "cagra":
+            if metric in ("cosine", "inner_product"):
+                # the reference's cagra is sqeuclidean only (knn.py:1521-1524)
+                raise ValueError(
+                    f"cagra supports euclidean/l2/sqeuclidean, not {metric!r}"
+                )
             search = self._make_cagra_search(algo_params)
         else:
             raise ValueError(f"unsupported ANN algorithm {algo!r}")
-        return self._kneighbors_impl(query_df, search)
+        return self._kneighbors_impl(
+            query_df, search, key_to_dist=lambda key: _key_to_dist(key, metric)
+        )
 
     # -- CAGRA-equivalent graph ANN ---------------------------------------
     def _make_cagra_search(self, algo_params: Dict[str, Any]):
@@ -429,33 +510,44 @@ class ApproximateNearestNeighborsModel(_ANNModelParams, _NNModelBase):
         labels, _, _, _ = kmeans_assign_reduce(Xt, C, x_sq)
         return C, labels.to(torch.int64)
 
-    def _make_ivfflat_search(self, algo_params: Dict[str, Any]):
+    def _make_ivfflat_search(self, algo_params: Dict[str, Any], metric: str = "euclidean"):
         def search(Qt: torch.Tensor, X: np.ndarray, k: int):
             from ..parallel.context import get_comm
 
             device = get_comm().device
             Xt = to_device_tensor(np.ascontiguousarray(X, dtype=np.float32), device)
+            if metric == "cosine":
+                Xt, Qt = _normalize_rows(Xt), _normalize_rows(Qt)
             n = Xt.shape[0]
             nlist = int(algo_params.get("nlist", self._default_nlist(n)))
             nprobe = int(algo_params.get("nprobe", max(1, nlist // 16)))
             C, labels = self._build_coarse(Xt, nlist)
-            return _ivf_search(Qt, Xt, C, labels, nlist, nprobe, k)
+            mode = _metric_mode(metric)
+            return _ivf_search(
+                Qt, Xt, C, labels, nlist, nprobe, k, mode,
+                use_kernel=_ivf_kernel_wanted(metric, Qt, Xt, k),
+            )
 
         return search
 
     # -- IVF-PQ ------------------------------------------------------------
-    def _make_ivfpq_search(self, algo_params: Dict[str, Any]):
+    def _make_ivfpq_search(self, algo_params: Dict[str, Any], metric: str = "euclidean"):
         """IVF-PQ with exact refine (reference ivf_pq + refine,
         knn.py:1512-1515,1643-1651): residual product quantization —
         per-subspace 256-centroid codebooks trained on coarse residuals,
         uint8 codes, per-query ADC lookup-table candidate scan over the
-        probed lists, then exact re-rank of refine_ratio*k candidates."""
+        probed lists, then exact re-rank of refine_ratio*k candidates by
+        the true metric. cosine runs the L2 pipeline on unit-normalised
+        rows; inner_product scans with the dot-product ADC form."""
+        mode = _metric_mode(metric)
 
         def search(Qt: torch.Tensor, X: np.ndarray, k: int):
             from ..parallel.context import get_comm
 
             device = get_comm().device
             Xt = to_device_tensor(np.ascontiguousarray(X, dtype=np.float32), device)
+            if metric == "cosine":
+                Xt, Qt = _normalize_rows(Xt), _normalize_rows(Qt)
             n, d = Xt.shape
             nlist = int(algo_params.get("nlist", self._default_nlist(n)))
             nprobe = int(algo_params.get("nprobe", max(1, nlist // 16)))
@@ -468,17 +560,20 @@ class ApproximateNearestNeighborsModel(_ANNModelParams, _NNModelBase):
             resid = Xt - C[labels]
             codebooks, codes = _pq_encode(resid, m_sub)
             d_c, i_c = _ivfpq_scan(
-                Qt, C, labels, codebooks, codes, nlist, nprobe, k_cand
+                Qt, C, labels, codebooks, codes, nlist, nprobe, k_cand, mode
             )
             # exact refine on candidates (full-precision vectors resident)
             rows = torch.arange(Qt.shape[0], device=device)[:, None]
             cand = Xt[i_c.clamp(min=0)]  # [q, k_cand, d]
-            d_exact = ((Qt[:, None, :] - cand) ** 2).sum(dim=2)
+            if mode == _MODE_DOT:
+                d_exact = -(Qt[:, None, :] * cand).sum(dim=2)
+            else:
+                d_exact = ((Qt[:, None, :] - cand) ** 2).sum(dim=2)
             d_exact = torch.where(
                 i_c >= 0, d_exact, torch.full_like(d_exact, float("inf"))
             )
             vals, order = torch.topk(d_exact, min(k, k_cand), dim=1, largest=False)
-            return torch.sqrt(torch.clamp(vals, min=0)), i_c[rows, order]
+            return vals, i_c[rows, order]
 
         return search
 
@@ -491,27 +586,30 @@ def _ivf_search(
     nlist: int,
     nprobe: int,
     k: int,
+    mode: int = _MODE_L2,
+    use_kernel: bool = False,
 ) -> Tuple[torch.Tensor, torch.Tensor]:
-    """Probe the nprobe nearest lists per query, maintain a running top-k."""
+    """Probe the nprobe best lists per query and keep a running top-k.
+    Returns (keys [nq, k], item rows [nq, k]); the key is the squared L2
+    distance (mode 0) or -q.x (mode 1), +inf with row -1 for an empty slot.
+    `use_kernel` scans the probed lists with the fused `ivf_scan_topk` HIP
+    kernel; otherwise a torch loop over the lists."""
     device = Qt.device
     nq = Qt.shape[0]
     nprobe = min(nprobe, nlist)
-    cd = (
-        (Qt * Qt).sum(dim=1)[:, None]
-        + (C * C).sum(dim=1)[None, :]
-        - 2.0 * (Qt @ C.T)
-    )
-    probe = cd.topk(nprobe, dim=1, largest=False).indices  # [nq, nprobe]
-    probe_mask = torch.zeros((nq, nlist), dtype=torch.bool, device=device)
-    probe_mask.scatter_(1, probe, True)
-
-    best_d = torch.full((nq, k), float("inf"), device=device)
-    best_i = torch.full((nq, k), -1, dtype=torch.int64, device=device)
+    probe = _probe_lists(Qt, C, nprobe, mode)  # [nq, nprobe]
     order = torch.argsort(labels)
     sorted_labels = labels[order]
     boundaries = torch.searchsorted(
         sorted_labels, torch.arange(nlist + 1, device=device)
     )
+    if use_kernel:
+        return _ivf_scan_kernel(Qt, Xt, order, boundaries, probe, k, mode)
+
+    probe_mask = torch.zeros((nq, nlist), dtype=torch.bool, device=device)
+    probe_mask.scatter_(1, probe, True)
+    best_d = torch.full((nq, k), float("inf"), device=device)
+    best_i = torch.full((nq, k), -1, dtype=torch.int64, device=device)
     for l in range(nlist):
         s, e = int(boundaries[l]), int(boundaries[l + 1])
         if s == e:
@@ -523,11 +621,14 @@ def _ivf_search(
         kb = min(k, e - s)
         qb = Qt[qsel]
         xb = Xt[items]
-        d2 = (
-            (qb * qb).sum(dim=1)[:, None]
-            + (xb * xb).sum(dim=1)[None, :]
-            - 2.0 * (qb @ xb.T)
-        )
+        if mode == _MODE_DOT:
+            d2 = -(qb @ xb.T)
+        else:
+            d2 = (
+                (qb * qb).sum(dim=1)[:, None]
+                + (xb * xb).sum(dim=1)[None, :]
+                - 2.0 * (qb @ xb.T)
+            )
         vals, loc = torch.topk(d2, kb, dim=1, largest=False)
         ids = items[loc]
         # merge with running top-k
@@ -537,7 +638,84 @@ def _ivf_search(
         rows = torch.arange(qsel.numel(), device=device)[:, None]
         best_d[qsel] = mvals
         best_i[qsel] = cat_i[rows, morder]
-    return torch.sqrt(torch.clamp(best_d, min=0.0)), best_i
+    return best_d, best_i
+
+
+def _probe_lists(Qt: torch.Tensor, C: torch.Tensor, nprobe: int, mode: int) -> torch.Tensor:
+    """The nprobe lists to scan per query: smallest L2 to the list centre,
+    or largest q.c for the dot-product key."""
+    if mode == _MODE_DOT:
+        return (Qt @ C.T).topk(nprobe, dim=1, largest=True).indices
+    cd = (
+        (Qt * Qt).sum(dim=1)[:, None]
+        + (C * C).sum(dim=1)[None, :]
+        - 2.0 * (Qt @ C.T)
+    )
+    return cd.topk(nprobe, dim=1, largest=False).indices
+
+
+def _ivf_kernel_wanted(metric: str, Qt: torch.Tensor, Xt: torch.Tensor, k: int) -> bool:
+    """Route the IVF-Flat scan through the `ivf_scan_topk` kernel? On the GPU
+    (f32, k <= 64, d <= 2048) the metrics this kernel introduced use it;
+    euclidean/l2 keep the torch path unless SRML_IVF_KERNEL=1, and
+    SRML_IVF_KERNEL=0 forces the torch path for every metric."""
+    from ..ops.dispatch import use_hip
+
+    env = os.environ.get("SRML_IVF_KERNEL")
+    if env == "0" or not (Qt.is_cuda and use_hip(Qt, Xt)):
+        return False
+    if Qt.dtype != torch.float32 or Xt.dtype != torch.float32:
+        return False
+    if k > 64 or Qt.shape[1] > 2048:
+        return False
+    if metric in ("euclidean", "l2"):
+        return env == "1"
+    return True
+
+
+def _ivf_scan_kernel(
+    Qt: torch.Tensor,
+    Xt: torch.Tensor,
+    order: torch.Tensor,
+    boundaries: torch.Tensor,
+    probe: torch.Tensor,
+    k: int,
+    mode: int,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Kernel path of `_ivf_search`: one wave per (query, probed list) pair
+    over the list-sorted item copy, 64 key/position slots per pair, then one
+    topk over each query's nprobe*64 slots. The pairs are sorted by list so
+    neighbouring waves stream the same rows through L2; each pair still
+    writes its own [query, probe] output row."""
+    from ..ops.dispatch import hip_ops
+
+    ext = hip_ops()
+    nq, nprobe = probe.shape
+    Xs = Xt[order].contiguous()
+    list_off = boundaries.to(torch.int64).contiguous()
+    keys = torch.empty((nq, k), dtype=torch.float32, device=Qt.device)
+    ids = torch.empty((nq, k), dtype=torch.int64, device=Qt.device)
+    # key (f32) + position (i64) slot buffers stay under 512 MB per chunk
+    qchunk = max(1, (512 << 20) // (nprobe * 64 * 12))
+    for s in range(0, nq, qchunk):
+        e = min(nq, s + qchunk)
+        flat_list = probe[s:e].reshape(-1)
+        pair_out = torch.argsort(flat_list, stable=True)
+        pair_list = flat_list[pair_out].contiguous()
+        pair_q = torch.div(pair_out, nprobe, rounding_mode="floor")
+        part_key, part_pos = ext.ivf_scan_topk(
+            Qt[s:e].contiguous(), Xs, list_off, pair_q, pair_list, pair_out,
+            (e - s) * nprobe, k, mode,
+        )
+        part_key = part_key.view(e - s, nprobe * 64)
+        part_pos = part_pos.view(e - s, nprobe * 64)
+        # dead slots (lanes >= k hold -inf) and never-filled slots -> worst key
+        part_key = part_key.masked_fill(part_pos < 0, float("inf"))
+        vals, loc = torch.topk(part_key, k, dim=1, largest=False)
+        pos = part_pos.gather(1, loc)
+        keys[s:e] = vals
+        ids[s:e] = torch.where(pos >= 0, order[pos.clamp(min=0)], pos)
+    return keys, ids
 
 
 def _dedup_topk(ids: torch.Tensor, dists: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -655,7 +833,7 @@ def _graph_beam_search(
         beam, bd = _dedup_topk(cat_i, cat_d, itopk)
 
     ids2, vals2 = _dedup_topk(beam, bd, min(k, bd.shape[1]))
-    return torch.sqrt(torch.clamp(vals2, min=0.0)), ids2
+    return vals2, ids2  # squared-L2 keys
 
 
 def _pq_encode(resid: torch.Tensor, m_sub: int, n_codes: int = 256, iters: int = 8):
@@ -709,19 +887,17 @@ def _ivfpq_scan(
     nlist: int,
     nprobe: int,
     k: int,
+    mode: int = _MODE_L2,
 ) -> Tuple[torch.Tensor, torch.Tensor]:
     """ADC scan: per (query, probed list), approx dist = ||q - c_list||-part
-    + sum_m LUT[m, code_m] where LUT holds ||(q - c_list)_m - cb[m,j]||²."""
+    + sum_m LUT[m, code_m] where LUT holds ||(q - c_list)_m - cb[m,j]||².
+    mode 1 (dot-product key): -(q.c_list + sum_m q_m.cb[m, code_m]) — the
+    LUT holds the dots of the query itself, there is no residual query."""
     device = Qt.device
     nq = Qt.shape[0]
     m_sub, n_codes, ds = codebooks.shape
     nprobe = min(nprobe, nlist)
-    cd = (
-        (Qt * Qt).sum(dim=1)[:, None]
-        + (C * C).sum(dim=1)[None, :]
-        - 2.0 * (Qt @ C.T)
-    )
-    probe = cd.topk(nprobe, dim=1, largest=False).indices  # [nq, nprobe]
+    probe = _probe_lists(Qt, C, nprobe, mode)  # [nq, nprobe]
 
     order = torch.argsort(labels)
     sorted_labels = labels[order]
@@ -742,14 +918,23 @@ def _ivfpq_scan(
                 continue
             qsel = torch.nonzero(inv == ui).flatten()
             items = order[s:e]
-            qres = Qt[qsel] - C[l][None, :]  # [m_q, d] residual queries
-            # LUT [m_q, m_sub, 256]: ||qres_m||² - 2 qres_m . cb + ||cb||²
-            qr = qres.view(-1, m_sub, ds)
-            dots = torch.einsum("qmd,mcd->qmc", qr, codebooks)
-            lut = (qr * qr).sum(2)[:, :, None] - 2.0 * dots + cb_sq[None, :, :]
+            if mode == _MODE_DOT:
+                qb = Qt[qsel]
+                qr = qb.reshape(-1, m_sub, ds)
+                lut = -torch.einsum("qmd,mcd->qmc", qr, codebooks)
+                base = -(qb @ C[l])  # [m_q]
+            else:
+                qres = Qt[qsel] - C[l][None, :]  # [m_q, d] residual queries
+                # LUT [m_q, m_sub, 256]: ||qres_m||² - 2 qres_m . cb + ||cb||²
+                qr = qres.view(-1, m_sub, ds)
+                dots = torch.einsum("qmd,mcd->qmc", qr, codebooks)
+                lut = (qr * qr).sum(2)[:, :, None] - 2.0 * dots + cb_sq[None, :, :]
+                base = None
             lc = codes[items].long()  # [n_l, m_sub]
             # approx dists [m_q, n_l] = sum_m lut[q, m, code]
             d_apx = torch.zeros(qsel.numel(), items.numel(), device=device)
+            if base is not None:
+                d_apx += base[:, None]
             for m in range(m_sub):
                 d_apx += lut[:, m, :].gather(
                     1, lc[:, m][None, :].expand(qsel.numel(), -1)

@@ -20,7 +20,35 @@ CLASSES = [
     "UMAP", "UMAPModel",
 ]
 
-TAIL = """## Evaluators
+TAIL = """## Metrics
+
+`ApproximateNearestNeighbors(metric=...)` / `setMetric` / `getMetric` \
+(reference knn.py:1007-1010). An unknown name raises `ValueError` from \
+`setMetric`, and from `kneighbors` when it came in through the constructor.
+
+| metric | ivfflat | ivfpq | cagra | `distances` column | order | empty slot |
+|---|---|---|---|---|---|---|
+| `euclidean`, `l2` | yes | yes | yes | L2 distance | ascending | `+inf`, id `-1` |
+| `sqeuclidean` | yes | yes | yes | squared L2 distance | ascending | `+inf`, id `-1` |
+| `cosine` | yes | yes | `ValueError` | `1 - cos` | ascending | `+inf`, id `-1` |
+| `inner_product` | yes | yes | `ValueError` | raw dot product `q.x` | descending | `-inf`, id `-1` |
+
+`cosine` normalises every row by `max(norm, 1e-30)`: a zero vector stays \
+zero and comes out at cosine distance 0.5 from everything. An empty slot \
+appears when fewer than `k` items are reachable through the probed lists. \
+Exact `NearestNeighbors` has no metric parameter (Euclidean, as in the \
+reference).
+
+`DBSCAN(metric=...)` (reference clustering.py:761):
+
+| metric | meaning |
+|---|---|
+| `euclidean` | `eps` bounds the L2 distance |
+| `cosine` | `eps` bounds `1 - cos`; a zero-norm row raises `ValueError` |
+
+Any other DBSCAN metric raises `ValueError` at `transform`.
+
+## Evaluators
 
 `RegressionEvaluator` (rmse|mse|r2|mae|var), `MulticlassClassificationEvaluator` \
 (f1|accuracy|weighted*|hammingLoss|logLoss + *ByLabel metrics via `metricLabel`), \
