@@ -229,6 +229,93 @@ def test_dbscan_sweep_matches_torch():
     assert mism <= n_rows * 0.003, f"{mism} label mismatches"
 
 
+def _dbscan_blob_case(n, d):
+    """6 unit-noise Gaussian blobs and a tie-free eps2, all on the CPU.
+
+    eps2 sits in the middle of the widest gap among the 200 sorted exact
+    (float64) pairwise squared distances around the 2 % quantile, so a kernel
+    whose f32 distance error is well below half that gap must reproduce the
+    float64 neighbourhoods exactly. Returns (X f32, D f64 [n,n], eps2,
+    half_gap, worst |f32 expansion form - f64|)."""
+    rng = np.random.default_rng(1)
+    centres = rng.normal(scale=2.0, size=(6, d))
+    X = (centres[rng.integers(0, 6, size=n)] + rng.normal(size=(n, d))).astype(np.float32)
+    X64 = X.astype(np.float64)
+    D = np.concatenate(  # direct differences, row-chunked to bound memory
+        [((X64[s : s + 64, None, :] - X64[None, :, :]) ** 2).sum(axis=2) for s in range(0, n, 64)]
+    )
+    flat = np.sort(D[np.triu_indices(n, 1)])  # each unordered pair once
+    q = int(0.02 * flat.size)
+    window = flat[q - 100 : q + 100]
+    gaps = np.diff(window)
+    g = int(np.argmax(gaps))
+    eps2 = float(0.5 * (window[g] + window[g + 1]))
+    half_gap = float(0.5 * gaps[g])
+    Xt = torch.from_numpy(X)
+    x_sq = (Xt * Xt).sum(dim=1)
+    d2_f32 = x_sq[:, None] + x_sq[None, :] - 2.0 * (Xt @ Xt.T)
+    f32_err = float((d2_f32.double() - torch.from_numpy(D)).abs().max())
+    return X, D, eps2, half_gap, f32_err
+
+
+@pytest.mark.parametrize(
+    "n,d",
+    [
+        (512, 128),  # all tiles full, d % 64 == 0: unguarded loads, 2 K-steps (one prefetch)
+        (700, 200),  # 4 K-steps with a d tail, row and column tails
+        (640, 64),   # single K-step: prologue only, no in-loop LDS write
+    ],
+)
+def test_dbscan_sweep_exact_on_blobs(ext, n, d):
+    """dbscan_sweep counts / min-core-labels equal the float64 reference
+    exactly on clustered data (neighbour counts 1..~100, hundreds of core
+    points), dense and through a pruned tile list."""
+    X_np, D, eps2, half_gap, f32_err = _dbscan_blob_case(n, d)
+    # precondition: the eps boundary is out of reach of f32 rounding
+    assert half_gap >= 5.0 * f32_err, (half_gap, f32_err)
+    near = D <= eps2
+    ref_counts = near.sum(axis=1).astype(np.int32)
+    min_pts = 5
+    core_np = ref_counts >= min_pts
+    assert ref_counts.max() >= 30 and core_np.sum() >= 100  # the data is not degenerate
+
+    dev = torch.device("cuda:0")
+    X = torch.from_numpy(X_np).to(dev)
+    x_sq = (X * X).sum(dim=1)
+    empty_u8 = torch.empty(0, dtype=torch.uint8, device=dev)
+    empty_i32 = torch.empty(0, dtype=torch.int32, device=dev)
+
+    # mode 0, dense, all rows
+    counts = ext.dbscan_sweep(
+        X, x_sq, 0, n, eps2, 0, empty_u8, empty_i32, empty_i32, empty_i32
+    )
+    assert np.array_equal(counts.cpu().numpy(), ref_counts)
+
+    # mode 1 on a row slice that starts off a 128 boundary
+    BIG = np.iinfo(np.int32).max
+    labels_np = np.where(core_np, np.arange(n), BIG).astype(np.int32)
+    row0, n_rows = 100, n - 150
+    got = ext.dbscan_sweep(
+        X, x_sq, row0, n_rows, eps2, 1,
+        torch.from_numpy(core_np.astype(np.uint8)).to(dev),
+        torch.from_numpy(labels_np).to(dev), empty_i32, empty_i32,
+    )
+    ref = np.where(
+        near[row0 : row0 + n_rows] & core_np[None, :], labels_np[None, :], BIG
+    ).min(axis=1)
+    assert np.array_equal(got.cpu().numpy(), ref)
+
+    # mode 0 through a tile list naming every column tile, in reverse order
+    n_tiles = (n + 127) // 128
+    tile_idx = torch.arange(n_tiles - 1, -1, -1, dtype=torch.int32).repeat(n_tiles).to(dev)
+    tile_off = (torch.arange(n_tiles + 1, dtype=torch.int32) * n_tiles).to(dev)
+    pruned = ext.dbscan_sweep(
+        X, x_sq, 0, n, eps2, 0, empty_u8, empty_i32, tile_idx, tile_off
+    )
+    assert torch.equal(pruned, counts)
+    assert np.array_equal(pruned.cpu().numpy(), ref_counts)
+
+
 @pytest.mark.parametrize("n,B", [(100000, 1), (50000, 977), (200000, 4096)])
 def test_rf_partition_matches_sort(ext, n, B):
     g = torch.Generator().manual_seed(3)
@@ -453,10 +540,10 @@ def test_kmeans_gemm_argmin_nk_matches_fused(ext, n, d, k):
     X = _rand(n, d, seed=31)
     C = _rand(k, d, seed=32)
     x_sq = (X * X).sum(dim=1)
-    from spark_rapids_ml_amd.ops.kmeans import _assign_gemm_nk
+    from spark_rapids_ml_amd.ops.kmeans import _assign_gemm
 
-    labels_g, inertia_g = _assign_gemm_nk(ext, X, C, x_sq, n, k,
-                                          max_dots_bytes=4 << 20)  # force chunking
+    labels_g, inertia_g = _assign_gemm(ext, X, C, x_sq, n, k, layout="nk",
+                                       max_dots_bytes=4 << 20)  # force chunking
     labels_f, _md, inertia_f = ext.kmeans_assign(X, C, x_sq)
     mism = (labels_g != labels_f)
     if bool(mism.any()):

@@ -1,6 +1,7 @@
-"""Standalone timing harness for the KMeans assign kernel variants.
+"""Standalone timing harness for the fused KMeans assign kernel.
 
-Usage (on a GPU box):  [SRML_KMEANS_VARIANT=b|2|3|s] python tools/time_assign.py
+Usage (on a GPU box):  python tools/time_assign.py
+Calls `ext.kmeans_assign` directly, so SRML_KMEANS_VARIANT plays no part.
 Measures the 1M x 3000, k=1000 assign (the bench.py hot kernel) and checks
 labels against a torch cdist argmin on a slice.
 """
