@@ -5,10 +5,11 @@ trees are divided across workers (`_estimators_per_worker`, tree.py:330-341),
 each worker fits its sub-forest on its LOCAL partition only (single-GPU cuML
 RF, histogram split finding with n_bins≤128), the serialized sub-forests are
 allGather'ed and concatenated (tree.py:424-460). The trainer here is a
-from-scratch histogram forest in torch (CPU/ROCm; the histogram build is the
-HIP-kernel candidate): depth-wise frontier, per-(node,feature,bin) class
-counts / moment stats via scatter-add, vectorized gain scan, per-node
-feature subsampling.
+from-scratch histogram forest: `_grow_forest` drives a depth-wise frontier
+with per-node feature subsampling over one node arena; how a level's
+per-(node,feature,bin) histograms, gain scan and row rerouting are computed
+(HIP kernels on gfx950, torch on CPU) is the backend's business in
+`ops/forest.py`, as is forest inference.
 
 Forest serialization is an own format (arrays per tree: feature, threshold,
 children, leaf values) playing the role of treelite bytes + JSON dump
@@ -27,6 +28,7 @@ import torch
 
 from ..core import Estimator, Model, _FitContext
 from ..data import to_device_tensor
+from ..ops.forest import RFTimer, forest_backend, forest_predict
 from ..params import (
     HasFeaturesCol,
     HasFeaturesCols,
@@ -120,17 +122,6 @@ class _RandomForestParams(HasFeaturesCol, HasFeaturesCols, HasLabelCol, HasPredi
 
     def getMaxDepth(self) -> int:
         return self.getOrDefault("maxDepth")
-
-
-def _max_lastdim(t: torch.Tensor):
-    """(values, indices) over the last dim. torch-CPU's indexed max/argmax is
-    ~30x slower than numpy in this build; route CPU through numpy."""
-    if t.is_cuda:
-        return t.max(dim=-1)
-    arr = t.detach().numpy()
-    idx = np.argmax(arr, axis=-1)
-    vals = np.take_along_axis(arr, np.expand_dims(idx, -1), axis=-1).squeeze(-1)
-    return torch.from_numpy(np.ascontiguousarray(vals)), torch.from_numpy(idx.astype(np.int64))
 
 
 def _estimators_per_worker(n_estimators: int, world: int) -> List[int]:
@@ -373,7 +364,6 @@ def _grow_forest(
         else:
             counts = torch.bincount(y_idx, minlength=n_classes).to(torch.float32)
             root_vals = np.tile(as_numpy(counts), (n_trees, 1))
-        yf = None
     else:
         yf = y.to(torch.float32)
         if phys_all is not None:
@@ -385,75 +375,14 @@ def _grow_forest(
         root_vals = np.stack(
             [means, np.full(n_trees, float(per), np.float32)], axis=1
         )
-        y_idx = None
 
     tree.add_leaves(root_vals, tree_ids=np.arange(n_trees, dtype=np.int32))
     edges_np = as_numpy(edges)
     # virtual row v starts at its tree's root (arena ids 0..n_trees-1)
     node_of_row = t_of_v.clone()
-    sample_t = (
-        sample.contiguous()
-        if sample is not None
-        else torch.empty(0, dtype=torch.int32, device=dev)
-    )
-
-    # HIP histogram path (LDS-privatized, rows segment-sorted by node)
-    import os as _os
-
-    from ..ops.dispatch import has_hip_ops, use_hip
-
-    hip_hist = Xb.is_cuda and use_hip(Xb) and has_hip_ops()
-    _rf_debug = _os.environ.get("SRML_RF_DEBUG") == "1"
-    _rf_t = _os.environ.get("SRML_RF_DEBUG") == "2"
-    _acc: Dict[str, float] = {}
-
-    def _tick(label, t0):
-        if not _rf_t:
-            return 0.0
-        import time as _tm
-
-        if Xb.is_cuda:
-            torch.cuda.synchronize()
-        t = _tm.perf_counter()
-        _acc[label] = _acc.get(label, 0.0) + (t - t0)
-        return t
-
-    def _now():
-        if not _rf_t:
-            return 0.0
-        import time as _tm
-
-        if Xb.is_cuda:
-            torch.cuda.synchronize()
-        return _tm.perf_counter()
-    if _rf_debug:
-        print(f"[rf-debug] hip_hist={hip_hist} n={n} d={d} device={dev}", flush=True)
-    if hip_hist:
-        from ..ops.dispatch import hip_ops
-
-        ext = hip_ops()
-        y32 = y_idx.to(torch.int32) if task == "classification" else yf
-        # max|y| for the packed regression histogram cells, ONE sync per fit
-        y_max = (
-            float(yf.abs().max().item()) if task == "regression" and n else 0.0
-        )
-        if y_max <= 0.0 and task == "regression":
-            y_max = 1.0
-        C_ch = n_classes if task == "classification" else 2
-        # Measured dispatch (A/B in profiles/README.md): the row-lane
-        # kernel wins for classification (sqrt-sampled features, sorted
-        # bootstrap = dense segments), the feature-wide kernel wins for
-        # regression (1/3-sampled features); SRML_RF_HIST=old|fw overrides
-        _mode = _os.environ.get("SRML_RF_HIST")
-        _hist_old = (_mode == "old") or (_mode != "fw" and task == "classification")
-        if _hist_old:
-            fc_kernel = max(1, min(512, (30 * 1024 // 4) // max(1, n_bins * C_ch)))
-        else:
-            fc_kernel = max(1, min(32, (150 * 1024 // 4) // max(1, n_bins * C_ch)))
-        # column-major binned matrix for the histogram/reroute kernels: a
-        # node segment's row gathers stay inside dense per-feature cache
-        # lines (row-major fetched a ~47-line row to read ~54 sampled bytes)
-        Xcm = Xb.T.contiguous()
+    levels = forest_backend(Xb, y, task, n_classes, n_bins, sample, feat_chunk)
+    timer = RFTimer(dev)
+    timer.debug(f"{levels.label} n={n} d={d} device={dev}")
     frontier = list(range(n_trees))  # arena node ids still splittable
 
     for depth in range(max_depth):
@@ -467,45 +396,18 @@ def _grow_forest(
             # map node id -> local 0..B-1 (rows not in batch -> -1)
             lut = torch.full((tree.n_nodes,), -1, dtype=torch.int64, device=dev)
             lut[batch_t] = torch.arange(B, dtype=torch.int64, device=dev)
-            if hip_hist:
-                _t0 = _now()
-                # counting-sort partition kernel: one pass for counts, one
-                # scatter — replaces sort+nonzero+gathers (rf_partition)
-                perm, seg_off = ext.rf_partition(node_of_row, lut, B)
-                _tick("partition", _t0)
-                # no host sync here: an all-empty batch flows through as
-                # no-op kernels and an empty split set
-                rows = loc = yb = None
-            else:
-                local = lut[node_of_row]
-                in_batch = local >= 0
-                rows = torch.nonzero(in_batch).flatten()
-                if rows.numel() == 0:
-                    continue
-                loc = local[rows]
-                # virtual -> physical rows for feature/label gathers
-                prows = phys_all[rows] if phys_all is not None else rows % n
-                if task == "classification":
-                    yb = y_idx[prows]
-                else:
-                    yb = yf[prows]
-
-            best_gain = torch.full((B,), -1.0, dtype=torch.float32, device=dev)
-            best_feat = torch.full((B,), -1, dtype=torch.int64, device=dev)
-            best_bin = torch.full((B,), -1, dtype=torch.int64, device=dev)
-            best_lcnt = torch.zeros((B,), dtype=torch.float32, device=dev)
-            if task == "classification":
-                best_lval = torch.zeros((B, n_classes), dtype=torch.float32, device=dev)
-                best_rval = torch.zeros((B, n_classes), dtype=torch.float32, device=dev)
-            else:
-                best_lval = torch.zeros((B, 2), dtype=torch.float32, device=dev)
-                best_rval = torch.zeros((B, 2), dtype=torch.float32, device=dev)
+            timer.mark()
+            # a backend that knows the batch holds no rows skips it here,
+            # before any random draw
+            if not levels.partition(node_of_row, lut, B):
+                continue
+            timer.tick("partition")
 
             # per-node sampled feature subset: histograms are built ONLY for
             # sampled features (a gather per node), not all d then masked —
             # at sqrt(d) sampling this is the d/sqrt(d)-fold work saver the
             # reference gets from cuML's per-node sampling.
-            _t0 = _now()
+            feat_sel = None
             if max_features < d:
                 scores = torch.rand((B, d), generator=gen, device=dev)
                 # uniform subset without replacement: topk of random scores
@@ -515,116 +417,11 @@ def _grow_forest(
                     feat_sel = scores.topk(max_features, dim=1).indices
                 else:
                     feat_sel = scores.argsort(dim=1)[:, :max_features]
-                if hip_hist and not _hist_old:
-                    # feature-wide kernel wants SORTED per-node subsets: a
-                    # wave-load then spans consecutive row bytes (avg gap
-                    # d/mf) instead of the whole row
-                    feat_sel = feat_sel.sort(dim=1).values
-                _tick("feat_sel", _t0)
-                mf = max_features
-                Xb_rows = None  # sampled path reads only selected bytes
-            else:
-                feat_sel = None
-                mf = d
-                Xb_rows = None
-            if hip_hist:
-                fsel32 = (
-                    feat_sel.to(torch.int32).contiguous()
-                    if feat_sel is not None
-                    else torch.empty((0, 0), dtype=torch.int32, device=dev)
-                )
-                fc_step = fc_kernel
-            else:
-                if feat_sel is None:
-                    Xb_rows = Xb[prows]
-                fc_step = feat_chunk
-            _t0 = _now()
-            for f0 in range(0, mf, fc_step):
-                f1 = min(mf, f0 + fc_step)
-                F = f1 - f0
-                if hip_hist:
-                    _hist_fn = ext.rf_histogram if _hist_old else ext.rf_histogram_fw
-                    _hist_x = Xcm if _hist_old else Xb
-                    H = _hist_fn(
-                        _hist_x, perm, seg_off, fsel32, y32, f0, F, n_bins,
-                        n_classes if task == "classification" else 0,
-                        sample_t, y_max if task == "regression" else 0.0,
-                    )
-                    if H.shape[3] <= 16:
-                        # fused gain scan + per-node best (kernel)
-                        g, fidx, sbin_b, lval_b, rval_b = ext.rf_best_split(
-                            H, min_leaf, task == "classification"
-                        )
-                        fidx = fidx.to(torch.int64)
-                        upd = g > best_gain
-                        best_gain = torch.where(upd, g, best_gain)
-                        ar = torch.arange(B, device=dev)
-                        if feat_sel is not None:
-                            chosen = feat_sel[ar, (fidx + f0).clamp(min=0)]
-                        else:
-                            chosen = fidx + f0
-                        best_feat = torch.where(upd, chosen, best_feat)
-                        best_bin = torch.where(upd, sbin_b.to(torch.int64), best_bin)
-                        if task == "regression":
-                            # kernel emits raw (count, sum); the tree stores
-                            # (mean, count) leaf values
-                            lc = torch.clamp(lval_b[:, 0], min=1e-12)
-                            rc = torch.clamp(rval_b[:, 0], min=1e-12)
-                            lval_b = torch.stack([lval_b[:, 1] / lc, lval_b[:, 0]], dim=1)
-                            rval_b = torch.stack([rval_b[:, 1] / rc, rval_b[:, 0]], dim=1)
-                        best_lval = torch.where(upd[:, None], lval_b, best_lval)
-                        best_rval = torch.where(upd[:, None], rval_b, best_rval)
-                        continue
-                    if task == "classification":
-                        gain, sbin, lval, rval, lcnt = _best_split_class(H, min_leaf)
-                    else:
-                        gain, sbin, lval, rval, lcnt = _best_split_reg(H, min_leaf)
-                elif task == "classification":
-                    if feat_sel is not None:
-                        sel = feat_sel[loc][:, f0:f1]
-                        bins = Xb[prows[:, None], sel].to(torch.int64)
-                    else:
-                        bins = Xb_rows[:, f0:f1].to(torch.int64)
-                    base = (loc[:, None] * F + torch.arange(F, device=dev)[None, :]) * n_bins + bins
-                    hist = torch.zeros(B * F * n_bins * n_classes, dtype=torch.float32, device=dev)
-                    idx = base * n_classes + yb[:, None]
-                    hist.index_add_(0, idx.flatten(), torch.ones(idx.numel(), device=dev))
-                    H = hist.view(B, F, n_bins, n_classes)
-                    gain, sbin, lval, rval, lcnt = _best_split_class(H, min_leaf)
-                else:
-                    if feat_sel is not None:
-                        sel = feat_sel[loc][:, f0:f1]
-                        bins = Xb[prows[:, None], sel].to(torch.int64)
-                    else:
-                        bins = Xb_rows[:, f0:f1].to(torch.int64)
-                    base = (loc[:, None] * F + torch.arange(F, device=dev)[None, :]) * n_bins + bins
-                    # (count, sum) only: the sum-of-squares terms cancel in
-                    # the variance-reduction gain (ls²/lc + rs²/rc - ts²/tc)
-                    hist2 = torch.zeros(B * F * n_bins, 2, dtype=torch.float32, device=dev)
-                    flat = base.flatten()
-                    src = torch.empty(bins.shape[0], 2, dtype=torch.float32, device=dev)
-                    src[:, 0] = 1.0
-                    src[:, 1] = yb
-                    hist2.index_add_(0, flat, src.repeat_interleave(F, dim=0) if F > 1 else src)
-                    H = hist2.view(B, F, n_bins, 2)
-                    gain, sbin, lval, rval, lcnt = _best_split_reg(H, min_leaf)
-                # best feature within chunk
-                g, fidx = _max_lastdim(gain)
-                upd = g > best_gain
-                best_gain = torch.where(upd, g, best_gain)
-                ar = torch.arange(B, device=dev)
-                if feat_sel is not None:
-                    chosen = feat_sel[ar, fidx + f0]
-                else:
-                    chosen = fidx + f0
-                best_feat = torch.where(upd, chosen, best_feat)
-                best_bin = torch.where(upd, sbin[ar, fidx], best_bin)
-                best_lcnt = torch.where(upd, lcnt[ar, fidx], best_lcnt)
-                best_lval = torch.where(upd[:, None], lval[ar, fidx], best_lval)
-                best_rval = torch.where(upd[:, None], rval[ar, fidx], best_rval)
-
-            _tick("hist_scan", _t0)
-            _t0 = _now()
+                timer.tick("feat_sel")
+            best_gain, best_feat, best_bin, best_lval, best_rval = levels.best_splits(
+                feat_sel, min(max_features, d), B, min_leaf
+            )
+            timer.tick("hist_scan")
             # materialize splits: fully vectorized (one bulk leaf append +
             # one set_splits per batch; the per-node loop was the depth-13
             # wall-clock bottleneck)
@@ -677,105 +474,23 @@ def _grow_forest(
                     rcount = rv[idxs].sum(axis=1)
                 new_frontier.extend(l_ids[lcount >= 2 * min_leaf].tolist())
                 new_frontier.extend(r_ids[rcount >= 2 * min_leaf].tolist())
-            _tick("materialize", _t0)
-            _t0 = _now()
+            timer.tick("materialize")
             # reroute rows of split nodes (touch only the split feature byte)
-            nid_t = torch.from_numpy(batch_np[idxs]).to(dev)
-            f_t = torch.from_numpy(fsel).to(dev)
-            b_t = torch.from_numpy(bsel).to(dev)
-            l_t = torch.from_numpy(l_ids).to(dev)
-            r_t = torch.from_numpy(r_ids).to(dev)
+            nid_t, f_t, b_t, l_t, r_t = (
+                torch.from_numpy(a).to(dev) for a in (batch_np[idxs], fsel, bsel, l_ids, r_ids)
+            )
             lut2 = torch.full((tree.n_nodes,), -1, dtype=torch.int64, device=dev)
             lut2[nid_t] = torch.arange(ns, dtype=torch.int64, device=dev)
-            if hip_hist:
-                # single-pass kernel: gather split byte + child write fused
-                ext.rf_reroute(
-                    node_of_row, lut2,
-                    f_t.to(torch.int32), b_t.to(torch.int32), l_t, r_t, Xcm,
-                    sample_t,
-                )
-            else:
-                sl = lut2[node_of_row]
-                mrows = torch.nonzero(sl >= 0).flatten()
-                srel = sl[mrows]
-                pm = phys_all[mrows] if phys_all is not None else mrows % n
-                go_left = Xb[pm, f_t[srel]].to(torch.int64) <= b_t[srel]
-                node_of_row[mrows] = torch.where(go_left, l_t[srel], r_t[srel])
-            _tick("reroute", _t0)
-        if _rf_t:
-            pass
-        if _rf_debug:
-            print(
-                f"[rf-debug] depth={depth} frontier={len(frontier)} -> "
-                f"{len(new_frontier)} nodes={tree.n_nodes}",
-                flush=True,
-            )
+            levels.reroute(node_of_row, lut2, f_t, b_t, l_t, r_t)
+            timer.tick("reroute")
+        timer.debug(
+            f"depth={depth} frontier={len(frontier)} -> "
+            f"{len(new_frontier)} nodes={tree.n_nodes}"
+        )
         frontier = new_frontier
-    if _rf_t:
-        print(f"[rf-times] {sorted(_acc.items(), key=lambda kv: -kv[1])}", flush=True)
+    timer.report()
 
     return tree.split_by_tree(n_trees)
-
-
-def _best_split_class(H: torch.Tensor, min_leaf: int):
-    """H: [B,F,nb,C] class counts. Returns per (B,F): best gain (impurity
-    decrease weighted by node fraction, Spark/CART gini), split bin, left/right
-    class-count values, left count."""
-    csum = H.cumsum(dim=2)  # left counts for split at bin b (bins <= b)
-    total = csum[:, :, -1:, :]  # [B,F,1,C]
-    left = csum[:, :, :-1, :]  # split bins 0..nb-2
-    right = total - left
-    lc = left.sum(dim=3)
-    rc = right.sum(dim=3)
-    nt = total.sum(dim=3)  # [B,F,1]
-    gini = lambda cnt, tot: 1.0 - ((cnt / torch.clamp(tot.unsqueeze(-1), min=1e-12)) ** 2).sum(
-        dim=-1
-    )
-    g_parent = gini(total, nt)  # [B,F,1]
-    g_left = gini(left, lc)
-    g_right = gini(right, rc)
-    ntc = torch.clamp(nt, min=1e-12)
-    gain = g_parent - (lc / ntc) * g_left - (rc / ntc) * g_right  # [B,F,nb-1]
-    valid = (lc >= min_leaf) & (rc >= min_leaf)
-    gain = torch.where(valid, gain, torch.full_like(gain, -1.0))
-    best_gain, best_bin = _max_lastdim(gain)  # [B,F]
-    B, F = best_gain.shape
-    ar_b = torch.arange(B, device=H.device)[:, None].expand(B, F)
-    ar_f = torch.arange(F, device=H.device)[None, :].expand(B, F)
-    lval = left[ar_b, ar_f, best_bin]  # [B,F,C]
-    rval = right[ar_b, ar_f, best_bin]
-    lcnt = lc[ar_b, ar_f, best_bin]
-    return best_gain, best_bin, lval, rval, lcnt
-
-
-def _best_split_reg(H: torch.Tensor, min_leaf: int):
-    """H: [B,F,nb,2] = (count,sum). Variance-reduction gain — the
-    sum-of-squares terms cancel across parent/children, leaving
-    (ls²/lc + rs²/rc - ts²/tc)/tc, so the histogram needs no y² channel."""
-    cs = H.cumsum(dim=2)
-    total = cs[:, :, -1:, :]
-    left = cs[:, :, :-1, :]
-    right = total - left
-    lc, ls = left[..., 0], left[..., 1]
-    rc, rs = right[..., 0], right[..., 1]
-    tc, ts = total[..., 0], total[..., 1]
-    lcc = torch.clamp(lc, min=1e-12)
-    rcc = torch.clamp(rc, min=1e-12)
-    tcc = torch.clamp(tc, min=1e-12)
-    gain = (ls * ls / lcc + rs * rs / rcc - ts * ts / tcc) / tcc
-    valid = (lc >= min_leaf) & (rc >= min_leaf)
-    gain = torch.where(valid, gain, torch.full_like(gain, -1.0))
-    best_gain, best_bin = _max_lastdim(gain)
-    B, F = best_gain.shape
-    ar_b = torch.arange(B, device=H.device)[:, None].expand(B, F)
-    ar_f = torch.arange(F, device=H.device)[None, :].expand(B, F)
-    lcb = lc[ar_b, ar_f, best_bin]
-    lsb = ls[ar_b, ar_f, best_bin]
-    rcb = rc[ar_b, ar_f, best_bin]
-    rsb = rs[ar_b, ar_f, best_bin]
-    lval = torch.stack([lsb / torch.clamp(lcb, min=1e-12), lcb], dim=-1)
-    rval = torch.stack([rsb / torch.clamp(rcb, min=1e-12), rcb], dim=-1)
-    return best_gain, best_bin, lval, rval, lcb
 
 
 # ---------------------------------------------------------------------------
@@ -828,24 +543,10 @@ class _RandomForestEstimator(_RandomForestParams, Estimator):
         bootstrap = bool(params["bootstrap"])
         max_samples = float(params["max_samples"])
 
-        import os as _os
-        import time as _time
-
-        _dbg = _os.environ.get("SRML_RF_DEBUG") == "1"
-
-        def _phase(label: str, t0: float) -> float:
-            if _dbg:
-                if ctx.device.type == "cuda":
-                    torch.cuda.synchronize(ctx.device)
-                t = _time.perf_counter()
-                print(f"[rf-phase] {label}: {t - t0:.3f}s", flush=True)
-                return t
-            return t0
-
-        _t = _time.perf_counter()
+        timer = RFTimer(ctx.device)
         Xt = ctx.device_tensor(np.asarray(X, dtype=np.float32))
         n, d = Xt.shape
-        _t = _phase("ingest_h2d", _t)
+        timer.phase("ingest_h2d")
 
         if self._task == "classification":
             y_local = np.asarray(y)
@@ -861,9 +562,9 @@ class _RandomForestEstimator(_RandomForestParams, Estimator):
             yt = to_device_tensor(np.asarray(y, dtype=np.float32), ctx.device)
 
         edges = _compute_bin_edges(Xt, n_bins, comm, seed=seed)
-        _t = _phase("bin_edges", _t)
+        timer.phase("bin_edges")
         Xb = _bin_data(Xt, edges)
-        _t = _phase("bin_data", _t)
+        timer.phase("bin_data")
         max_features = _resolve_max_features(str(params["max_features"]), d, self._task)
 
         counts = _estimators_per_worker(n_estimators, comm.world_size)
@@ -922,7 +623,7 @@ class _RandomForestEstimator(_RandomForestParams, Estimator):
                         gen,
                         n_trees=g_trees,
                         sample=sample,
-                        node_batch=int(params.get("max_batch_size", 4096)),
+                        node_batch=int(params["max_batch_size"]),
                     )
                 )
                 t0g += g_trees
@@ -942,9 +643,7 @@ class _RandomForestEstimator(_RandomForestParams, Estimator):
                 }
                 for _ in range(my_trees)
             ]
-        _t = _phase("grow_trees_total", _t)
-
-        _t = _phase("grow_trees", _t)
+        timer.phase("grow_trees_total")
         # merge sub-forests (reference allGathers treelite bytes, tree.py:424-447)
         blobs = comm.allgather_obj(pickle.dumps(trees, protocol=4))
         forest: List[Dict[str, np.ndarray]] = []
@@ -1099,64 +798,14 @@ class _RandomForestModel(_RandomForestParams, Model):
         return arena
 
     def _predict_raw(self, X: Any) -> torch.Tensor:
-        """Forest inference. GPU: the fil_predict HIP kernel — one thread
-        walks every tree for its row over a flattened node arena (the
-        reference's FIL predict, tree.py:709-721). CPU fallback: vectorized
-        level-wise torch traversal. Returns [n, C] vote sums
-        (classification) or [n] mean."""
-        from ..ops.dispatch import has_hip_ops, hip_ops, use_hip
+        """Forest inference (`ops.forest.forest_predict`). Returns [n, C]
+        vote sums (classification) or the [n] sum of tree means."""
         from ..parallel.context import get_comm
 
-        device = get_comm().device
-        Xt = to_device_tensor(np.ascontiguousarray(X, dtype=np.float32), device)
-        n = Xt.shape[0]
-        vw = self.numClasses if self._task == "classification" else 2
-        if (
-            Xt.is_cuda
-            and use_hip(Xt)
-            and has_hip_ops()
-            and 0 < vw <= 16
-            and n > 0
-            and self.numTrees > 0
-        ):
-            a = self._device_arena(device)
-            out = hip_ops().fil_predict(
-                Xt.contiguous(), a["feat"], a["thr"], a["left"], a["right"],
-                a["value"], a["roots"], self._task == "classification",
-            )
-            if self._task == "classification":
-                return out
-            return out[:, 0]
-        if self._task == "classification":
-            acc = torch.zeros((n, self.numClasses), dtype=torch.float32, device=device)
-        else:
-            acc = torch.zeros(n, dtype=torch.float32, device=device)
-        for t in self.trees:
-            feature = torch.from_numpy(t["feature"]).to(device, torch.int64)
-            thr = torch.from_numpy(t["threshold"]).to(device)
-            left = torch.from_numpy(t["left"]).to(device, torch.int64)
-            right = torch.from_numpy(t["right"]).to(device, torch.int64)
-            leaf = torch.from_numpy(t["is_leaf"]).to(device)
-            value = torch.from_numpy(t["value"]).to(device)
-            node = torch.zeros(n, dtype=torch.int64, device=device)
-            while True:
-                at_leaf = leaf[node]
-                if bool(at_leaf.all()):
-                    break
-                f = feature[node].clamp(min=0)
-                xv = Xt.gather(1, f.view(-1, 1)).flatten()
-                # strict <: training partitions on bin(x) <= b  <=>  x <
-                # edges[b] (=stored threshold), so rows equal to the
-                # threshold went RIGHT during fit
-                go_left = xv < thr[node]
-                nxt = torch.where(go_left, left[node], right[node])
-                node = torch.where(at_leaf, node, nxt)
-            v = value[node]
-            if self._task == "classification":
-                acc += v / torch.clamp(v.sum(dim=1, keepdim=True), min=1e-12)
-            else:
-                acc += v[:, 0]
-        return acc
+        Xt = to_device_tensor(np.ascontiguousarray(X, dtype=np.float32), get_comm().device)
+        return forest_predict(
+            Xt, self.trees, self._task, self.numClasses, self._device_arena
+        )
 
     def predictLeaf(self, value) -> np.ndarray:
         """Leaf ordinal per tree for one feature vector (reference

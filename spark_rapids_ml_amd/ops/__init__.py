@@ -16,6 +16,7 @@ from .kmeans import kmeans_assign_reduce, kmeans_predict
 from .linalg import gram, xty_gram, eigh_sym, sign_flip
 from .glm import logistic_grad_loss, linear_grad_loss
 from .knn import knn_topk
+from .forest import forest_backend, forest_predict, forest_traverse
 
 __all__ = [
     "has_hip_ops",
@@ -32,4 +33,7 @@ __all__ = [
     "logistic_grad_loss",
     "knn_topk",
     "linear_grad_loss",
+    "forest_backend",
+    "forest_predict",
+    "forest_traverse",
 ]

@@ -138,10 +138,6 @@ def test_rf_histogram_matches_ref(ext, task, nc):
             sel = feat_sel[b]
             for q in range(mf):
                 bins = Xb[m][:, sel[q]].long()
-                for c in range(nc):
-                    ref[b, q].index_add_(
-                        0, bins[y[m] == c], torch.ones(int((y[m] == c).sum())).cuda()
-                    ) if False else None
                 ref[b, q] = torch.zeros(nb, nc).cuda().index_put_(
                     (bins, y[m].long()), torch.ones(len(bins)).cuda(), accumulate=True
                 )
@@ -163,7 +159,7 @@ def test_rf_histogram_matches_ref(ext, task, nc):
 
 @pytest.mark.parametrize("classif,C", [(True, 3), (False, 2)])
 def test_rf_best_split_matches_ref(ext, classif, C):
-    from spark_rapids_ml_amd.models.tree import _best_split_class, _best_split_reg, _max_lastdim
+    from spark_rapids_ml_amd.ops.forest import _best_split_class, _best_split_reg, _max_lastdim
 
     g = torch.Generator().manual_seed(1)
     B, F, nb = 9, 23, 32
@@ -434,6 +430,7 @@ def test_fil_predict_matches_torch_traversal(ext, task):
 
     from spark_rapids_ml_amd import RandomForestClassifier, RandomForestRegressor
     from spark_rapids_ml_amd.data import DataFrame
+    from spark_rapids_ml_amd.ops.forest import forest_traverse
 
     if task == "classification":
         X, y = make_classification(n_samples=3000, n_features=12, n_classes=3,
@@ -450,34 +447,7 @@ def test_fil_predict_matches_torch_traversal(ext, task):
     got = m._predict_raw(X)  # GPU -> fil kernel path
 
     # torch reference traversal on device
-    device = Xt.device
-    n = Xt.shape[0]
-    if task == "classification":
-        ref = torch.zeros((n, m.numClasses), dtype=torch.float32, device=device)
-    else:
-        ref = torch.zeros(n, dtype=torch.float32, device=device)
-    for t in m.trees:
-        feature = torch.from_numpy(t["feature"]).to(device, torch.int64)
-        thr = torch.from_numpy(t["threshold"]).to(device)
-        left = torch.from_numpy(t["left"]).to(device, torch.int64)
-        right = torch.from_numpy(t["right"]).to(device, torch.int64)
-        leaf = torch.from_numpy(t["is_leaf"]).to(device)
-        value = torch.from_numpy(t["value"]).to(device)
-        node = torch.zeros(n, dtype=torch.int64, device=device)
-        while True:
-            at_leaf = leaf[node]
-            if bool(at_leaf.all()):
-                break
-            f = feature[node].clamp(min=0)
-            xv = Xt.gather(1, f.view(-1, 1)).flatten()
-            go_left = xv < thr[node]
-            nxt = torch.where(go_left, left[node], right[node])
-            node = torch.where(at_leaf, node, nxt)
-        v = value[node]
-        if task == "classification":
-            ref += v / torch.clamp(v.sum(dim=1, keepdim=True), min=1e-12)
-        else:
-            ref += v[:, 0]
+    ref = forest_traverse(Xt, m.trees, task, m.numClasses)
     assert torch.allclose(got, ref, rtol=1e-4, atol=1e-4)
 
 
