@@ -35,6 +35,7 @@ from ..params import (
 )
 from ..data import to_device_tensor
 from ..ops import kmeans_assign_reduce, kmeans_predict
+from ..ops.dbscan import dbscan_backend, dbscan_labels
 from ..ops.torch_ref import pairwise_sq_dists
 from ..utils import as_numpy
 
@@ -427,8 +428,6 @@ class KMeansModel(_KMeansParams, Model):
         C = torch.from_numpy(
             np.ascontiguousarray(self.cluster_centers_, dtype=np.float32)
         ).to(comm.device)
-        from ..ops.torch_ref import pairwise_sq_dists
-
         local = 0.0
         for s0 in range(0, Xt.shape[0], 1 << 16):
             d2 = pairwise_sq_dists(Xt[s0 : s0 + (1 << 16)], C)
@@ -462,81 +461,6 @@ class KMeansModel(_KMeansParams, Model):
 # ---------------------------------------------------------------------------
 # DBSCAN
 # ---------------------------------------------------------------------------
-
-
-def _coarse_assign(Xf, K: int, iters: int = 4, seed: int = 0, chunk_bytes: int = 1 << 30):
-    """Coarse k-means partition used only to PERMUTE rows for ball-cover
-    tile pruning (reference algorithm="rbc", clustering.py:686-695). The
-    clustering result is exact regardless of this partition's quality — a
-    bad partition only prunes fewer tiles."""
-    n, d = Xf.shape
-    ids = torch.randperm(n, generator=torch.Generator().manual_seed(seed))[:K]
-    C = Xf[ids.to(Xf.device)].clone()
-    x_sq = (Xf * Xf).sum(dim=1)
-    asn = torch.empty(n, dtype=torch.int64, device=Xf.device)
-    chunk = max(1, chunk_bytes // max(1, K * 4))
-    for it in range(iters):
-        c_sq = (C * C).sum(dim=1)
-        for s in range(0, n, chunk):
-            e = min(n, s + chunk)
-            d2 = x_sq[s:e, None] + c_sq[None, :] - 2.0 * (Xf[s:e] @ C.T)
-            asn[s:e] = d2.argmin(dim=1)
-        if it + 1 < iters:
-            sums = torch.zeros_like(C)
-            cnts = torch.zeros(K, dtype=Xf.dtype, device=Xf.device)
-            sums.index_add_(0, asn, Xf)
-            cnts.index_add_(0, asn, torch.ones_like(x_sq))
-            nz = cnts > 0
-            C[nz] = sums[nz] / cnts[nz, None]
-    return asn
-
-
-def _tile_stats(Xp, B: int = 128):
-    """Bounding ball (center, radius) of each consecutive B-row tile of Xp."""
-    n, d = Xp.shape
-    nfull = (n // B) * B
-    cs, rs = [], []
-    if nfull:
-        Xv = Xp[:nfull].view(-1, B, d)
-        c = Xv.mean(dim=1)
-        r = (Xv - c[:, None, :]).pow(2).sum(dim=2).max(dim=1).values.sqrt()
-        cs.append(c)
-        rs.append(r)
-    if n > nfull:
-        c = Xp[nfull:].mean(dim=0, keepdim=True)
-        r = (Xp[nfull:] - c).pow(2).sum(dim=1).max().sqrt().reshape(1)
-        cs.append(c)
-        rs.append(r)
-    return torch.cat(cs, dim=0), torch.cat(rs, dim=0)
-
-
-def _tile_lists(Xp, row0: int, n_rows: int, eps: float, B: int = 128,
-                block_chunk: int = 8192):
-    """CSR list of admissible 128-column tiles per 128-row block of the
-    slice [row0, row0+n_rows): tile j can contain an eps-neighbor of a
-    point in row block i only if ||c_i - c_j|| <= r_i + r_j + eps
-    (triangle inequality — conservative, so the pruned sweep is exact).
-    Returns (tile_idx int32, tile_off int32 [n_blocks+1], kept_fraction)."""
-    cj, rj = _tile_stats(Xp, B)
-    ci, ri = _tile_stats(Xp[row0:row0 + n_rows], B)
-    nb, nt = ci.shape[0], cj.shape[0]
-    cj_sq = (cj * cj).sum(dim=1)
-    total = torch.zeros(1, dtype=torch.int64, device=Xp.device)
-    offs = [total]
-    idxs = []
-    for s in range(0, nb, block_chunk):
-        e = min(nb, s + block_chunk)
-        d2 = ((ci[s:e] * ci[s:e]).sum(dim=1)[:, None] + cj_sq[None, :]
-              - 2.0 * (ci[s:e] @ cj.T))
-        thr = ri[s:e, None] + rj[None, :] + eps
-        adm = d2 <= thr * thr * 1.0001 + 1e-5
-        idxs.append(adm.nonzero()[:, 1].to(torch.int32))
-        cum = adm.sum(dim=1).cumsum(0) + offs[-1][-1]
-        offs.append(cum)
-    tile_idx = torch.cat(idxs).contiguous()
-    tile_off = torch.cat(offs).to(torch.int32).contiguous()
-    kept = float(tile_idx.numel()) / float(max(1, nb * nt))
-    return tile_idx, tile_off, kept
 
 
 class _DBSCANParams(HasFeaturesCol, HasFeaturesCols, HasPredictionCol, HasIDCol):
@@ -679,130 +603,6 @@ class DBSCANModel(_DBSCANParams, Model):
     def _transform_array(self, X: Any) -> np.ndarray:  # pragma: no cover - unused
         raise NotImplementedError("DBSCANModel clusters via transform()")
 
-    def _cluster_hip(self, Xf, x_sq, off, n_local, comm, eps2, min_samples):
-        """GPU path: three uses of the fused dbscan_sweep kernel (core
-        counting, min-label sweeps to fixpoint, border assignment). Exact:
-        every sweep reduces over the FULL eps-adjacency; no capped-graph
-        approximation. The torch path below materializes [chunk, n] masked
-        label tensors — the kernel keeps distances in registers and reduces
-        into a 128-entry LDS accumulator instead.
-
-        algorithm="rbc" (reference clustering.py:686-695): rows are permuted
-        by a coarse k-means partition so each 128-row block / 128-column
-        tile has a tight bounding ball, and every sweep walks only the
-        column tiles admissible by the triangle inequality — same labels,
-        a fraction of the O(N²) work when the data actually clusters."""
-        import math
-        import os as _os
-
-        import torch
-
-        from ..ops.dispatch import hip_ops
-
-        ext = hip_ops()
-        device = Xf.device
-        n = Xf.shape[0]
-        BIG = torch.iinfo(torch.int32).max
-        empty_u8 = torch.empty(0, dtype=torch.uint8, device=device)
-        empty_i32 = torch.empty(0, dtype=torch.int32, device=device)
-        _dbg = _os.environ.get("SRML_DBSCAN_DEBUG") == "1"
-
-        algo = str(self.getOrDefault("algorithm") or "brute").lower()
-        perm = None
-        tile_idx, tile_off = empty_i32, empty_i32
-        wo, wn = off, n_local  # working-order slice owned by this rank
-        if algo == "rbc" and n >= 4096:
-            K = max(16, min(4096, n // 256))
-            if comm.rank == 0:
-                perm = torch.argsort(_coarse_assign(Xf, K), stable=True)
-            else:
-                perm = torch.empty(n, dtype=torch.int64, device=device)
-            if comm.world_size > 1:
-                perm = comm.broadcast(perm, src=0)
-            Xf = Xf[perm].contiguous()
-            base, rem = divmod(n, comm.world_size)
-            wn = base + (1 if comm.rank < rem else 0)
-            wo = comm.rank * base + min(comm.rank, rem)
-            tile_idx, tile_off, kept = _tile_lists(Xf, wo, wn, math.sqrt(eps2))
-            if _dbg:
-                print(f"[dbscan] rbc kept {kept:.3f} of column tiles", flush=True)
-            if kept > 0.95:
-                # ball bound prunes nothing (e.g. uniform noise): dense loop
-                tile_idx, tile_off = empty_i32, empty_i32
-            x_sq = (Xf * Xf).sum(dim=1).contiguous()
-
-        counts = ext.dbscan_sweep(
-            Xf, x_sq, wo, wn, eps2, 0, empty_u8, empty_i32, tile_idx, tile_off
-        )
-        core_local = counts >= min_samples
-        core_full = torch.cat(
-            comm.allgather_rows(core_local.to(torch.uint8)), dim=0
-        ).to(torch.bool)
-        if not bool(core_full.any()):
-            # no core points anywhere -> every point is noise; the
-            # min-label propagation sweeps (2 more O(N^2) passes) are
-            # vacuous
-            return np.full(n_local, -1, dtype=np.int64)
-        core_u8 = core_full.to(torch.uint8).contiguous()
-
-        labels = torch.arange(n, dtype=torch.int32, device=device)
-        labels[~core_full] = BIG
-        core_ids = torch.nonzero(core_full).flatten()
-
-        def pointer_jump(lab):
-            for _ in range(8):
-                cur = lab[core_ids]
-                tgt = lab[cur.long().clamp(max=n - 1)]
-                tgt = torch.where(cur < BIG, tgt, cur)
-                upd = torch.minimum(cur, tgt)
-                if bool((upd == cur).all()):
-                    break
-                lab[core_ids] = upd
-            return lab
-
-        out = None
-        for _sweep in range(64):
-            out = ext.dbscan_sweep(
-                Xf, x_sq, wo, wn, eps2, 1, core_u8, labels.contiguous(),
-                tile_idx, tile_off,
-            )
-            new_full = torch.full((n,), BIG, dtype=torch.int32, device=device)
-            if wn:
-                mine = labels[wo : wo + wn]
-                new_full[wo : wo + wn] = torch.where(
-                    core_local, torch.minimum(mine, out), mine
-                )
-            new_full = comm.allreduce_t(new_full, "min")
-            new_full[~core_full] = BIG
-            new_full = pointer_jump(new_full)
-            if bool((new_full == labels).all()):
-                if _dbg:
-                    print(f"[dbscan] converged after {_sweep + 1} label sweeps", flush=True)
-                break
-            labels = new_full
-
-        # border points: `out` was produced by the final (converged) sweep =
-        # min core-neighbor label over the full adjacency
-        final_work = torch.full((wn,), -1, dtype=torch.int64, device=device)
-        if wn:
-            border_lab = torch.where(out < BIG, out.to(torch.int64), final_work)
-            final_work = torch.where(
-                core_local, labels[wo : wo + wn].to(torch.int64), border_lab
-            )
-
-        all_parts = comm.allgather_obj(as_numpy(final_work))
-        full = np.concatenate(all_parts)  # working (possibly permuted) order
-        if perm is not None:
-            orig = np.empty_like(full)
-            orig[as_numpy(perm)] = full
-            full = orig
-        uniq = np.unique(full[full >= 0])
-        remap = {int(v): i for i, v in enumerate(uniq)}
-        return np.array(
-            [remap.get(int(v), -1) for v in full[off : off + n_local]],
-            dtype=np.int64,
-        )
-
     def _cluster(self, X_local: np.ndarray, comm, pdesc) -> np.ndarray:
         eps = float(self.getOrDefault("eps"))
         min_samples = int(self.getOrDefault("min_samples"))
@@ -820,7 +620,7 @@ class DBSCANModel(_DBSCANParams, Model):
         if metric == "cosine":
             # on unit rows ||u - v||^2 = 2 (1 - cos), so cosine distance
             # <= eps is squared L2 <= 2 eps and everything downstream
-            # (dbscan_sweep, the rbc ball cover, the torch path) serves
+            # (either sweep backend, the rbc ball cover) serves
             # unchanged. Every rank holds the full Xf: no collective needed.
             norms = Xf.norm(dim=1, keepdim=True)
             if n and bool((norms == 0).any()):
@@ -834,157 +634,8 @@ class DBSCANModel(_DBSCANParams, Model):
                 f"unsupported DBSCAN metric {metric!r}; expected euclidean or cosine"
             )
 
-        from ..ops.dispatch import use_hip
-
-        if use_hip(Xf):
-            x_sq_full = (Xf * Xf).sum(dim=1)
-            return self._cluster_hip(
-                Xf.contiguous(), x_sq_full.contiguous(), off, n_local, comm,
-                eps2, min_samples,
-            )
-
-        # batched adjacency: rows [off, off+n_local) vs all. The masked
-        # label tensors are [chunk, n] int64, so the chunk is bounded by
-        # bytes (reference max_mbytes_per_batch, clustering.py:673-682),
-        # defaulting to ~4 GB per intermediate.
-        mb = self.getOrDefault("max_mbytes_per_batch")
-        if mb:
-            chunk = max(1, int(mb * 1e6 / (8 * max(1, n))))
-        else:
-            chunk = max(64, min(4096, (4 << 30) // (8 * max(1, n))))
-        x_sq = (Xf * Xf).sum(dim=1)
-
-        core_local = torch.zeros(n_local, dtype=torch.bool, device=device)
-        for s in range(0, n_local, chunk):
-            e = min(n_local, s + chunk)
-            d2 = (
-                x_sq[off + s : off + e, None]
-                + x_sq[None, :]
-                - 2.0 * (Xf[off + s : off + e] @ Xf.T)
-            )
-            core_local[s:e] = (d2 <= eps2).sum(dim=1) >= min_samples
-
-        # global core mask (tensor all-gather of per-rank slices)
-        core_full = torch.cat(
-            comm.allgather_rows(core_local.to(torch.uint8)), dim=0
-        ).to(torch.bool)
-
-        # Capped edge list accelerates label propagation: each local row
-        # keeps its <=E_CAP nearest core neighbors (one distance pass). The
-        # capped graph may merge fewer components than the full eps-graph,
-        # so EXACTNESS comes from dense verification sweeps afterwards (full
-        # adjacency recompute) iterated to fixpoint — on clustered data the
-        # capped graph already gets the components right and verification
-        # confirms in a single pass.
-        E_CAP = 128
-        BIG = torch.iinfo(torch.int64).max
-        edge_src_l: list = []
-        edge_dst_l: list = []
-        for s in range(0, n_local, chunk):
-            e = min(n_local, s + chunk)
-            d2 = (
-                x_sq[off + s : off + e, None]
-                + x_sq[None, :]
-                - 2.0 * (Xf[off + s : off + e] @ Xf.T)
-            )
-            d2 = torch.where(core_full[None, :], d2, torch.full_like(d2, 3.4e38))
-            kk = min(E_CAP, n)
-            vals, idxs = torch.topk(d2, kk, dim=1, largest=False)
-            keep = vals <= eps2
-            rows_rep = (
-                torch.arange(s, e, device=device)[:, None].expand(-1, kk)[keep] + off
-            )
-            edge_src_l.append(rows_rep)
-            edge_dst_l.append(idxs[keep])
-        edge_src = torch.cat(edge_src_l) if edge_src_l else torch.empty(0, dtype=torch.int64, device=device)
-        edge_dst = torch.cat(edge_dst_l) if edge_dst_l else torch.empty(0, dtype=torch.int64, device=device)
-        del edge_src_l, edge_dst_l
-        src_is_core = core_full[edge_src]
-        ce_src = edge_src[src_is_core]
-        ce_dst = edge_dst[src_is_core]
-
-        labels = torch.arange(n, dtype=torch.int64, device=device)
-        labels[~core_full] = BIG
-        core_ids = torch.nonzero(core_full).flatten()
-
-        def pointer_jump(lab: torch.Tensor) -> torch.Tensor:
-            for _ in range(8):
-                tgt = lab[lab[core_ids].clamp(max=n - 1)]
-                valid = lab[core_ids] < BIG
-                tgt = torch.where(valid, tgt, lab[core_ids])
-                upd = torch.minimum(lab[core_ids], tgt)
-                if bool((upd == lab[core_ids]).all()):
-                    break
-                lab[core_ids] = upd
-            return lab
-
-        # phase 1: fast sweeps on the capped edge list
-        for _ in range(64):
-            new_full = torch.full((n,), BIG, dtype=torch.int64, device=device)
-            new_full[off : off + n_local] = labels[off : off + n_local]
-            if ce_src.numel():
-                new_full.scatter_reduce_(
-                    0, ce_src, labels[ce_dst], reduce="amin", include_self=True
-                )
-            new_full = comm.allreduce_t(new_full, "min")
-            new_full[~core_full] = BIG
-            new_full = pointer_jump(new_full)
-            if bool((new_full == labels).all()):
-                break
-            labels = new_full
-
-        # phase 2: dense verification sweeps to fixpoint (exactness: the
-        # full eps-adjacency is the ground truth the capped graph may miss)
-        for _ in range(64):
-            new_local = labels[off : off + n_local].clone()
-            for s in range(0, n_local, chunk):
-                e = min(n_local, s + chunk)
-                d2 = (
-                    x_sq[off + s : off + e, None]
-                    + x_sq[None, :]
-                    - 2.0 * (Xf[off + s : off + e] @ Xf.T)
-                )
-                lab_masked = torch.where(
-                    core_full[None, :] & (d2 <= eps2),
-                    labels[None, :].expand(e - s, n),
-                    torch.full((1,), BIG, dtype=torch.int64, device=device),
-                )
-                row_min = lab_masked.min(dim=1).values
-                row_core = core_local[s:e]
-                new_local[s:e] = torch.where(
-                    row_core, torch.minimum(new_local[s:e], row_min), new_local[s:e]
-                )
-            new_full = torch.full((n,), BIG, dtype=torch.int64, device=device)
-            new_full[off : off + n_local] = new_local
-            new_full = comm.allreduce_t(new_full, "min")
-            new_full[~core_full] = BIG
-            new_full = pointer_jump(new_full)
-            if bool((new_full == labels).all()):
-                break
-            labels = new_full
-
-        # border points: min core-neighbor label over the FULL adjacency
-        final_local = torch.full((n_local,), -1, dtype=torch.int64, device=device)
-        for s in range(0, n_local, chunk):
-            e = min(n_local, s + chunk)
-            d2 = (
-                x_sq[off + s : off + e, None]
-                + x_sq[None, :]
-                - 2.0 * (Xf[off + s : off + e] @ Xf.T)
-            )
-            lab_masked = torch.where(
-                core_full[None, :] & (d2 <= eps2),
-                labels[None, :].expand(e - s, n),
-                torch.full((1,), BIG, dtype=torch.int64, device=device),
-            )
-            row_min = lab_masked.min(dim=1).values
-            final_local[s:e] = torch.where(row_min < BIG, row_min, final_local[s:e])
-        final_local[core_local] = labels[off : off + n_local][core_local]
-
-        # relabel to consecutive ids ordered by first occurrence (global)
-        all_parts = comm.allgather_obj(as_numpy(final_local))
-        full = np.concatenate(all_parts)
-        uniq = np.unique(full[full >= 0])
-        remap = {int(v): i for i, v in enumerate(uniq)}
-        out = np.array([remap.get(int(v), -1) for v in as_numpy(final_local)], dtype=np.int64)
-        return out
+        backend = dbscan_backend(
+            Xf, off, n_local, comm, eps2,
+            self.getOrDefault("algorithm"), self.getOrDefault("max_mbytes_per_batch"),
+        )
+        return dbscan_labels(backend, comm, off, n_local, min_samples)

@@ -116,7 +116,7 @@ def test_dbscan_gpu_rbc_matches_brute():
     products in permuted row order, so pairs within float rounding of eps
     can flip (same 0.3% bound as test_dbscan_sweep_matches_torch); the
     pruning logic itself is proven exact on CPU in
-    test_cluster_hip_logic_with_fake_kernel."""
+    test_hip_driver_logic_with_fake_kernel."""
     from sklearn.cluster import DBSCAN as SkDBSCAN
     from sklearn.metrics import adjusted_rand_score
 

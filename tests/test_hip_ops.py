@@ -312,6 +312,45 @@ def test_dbscan_sweep_exact_on_blobs(ext, n, d):
     assert np.array_equal(pruned.cpu().numpy(), ref_counts)
 
 
+def test_dbscan_backends_agree_and_exact(ext):
+    """The HIP and the torch sweep backend give the same counts and
+    min-core-labels on the same device tensor and row slice, and both equal
+    the float64 reference exactly."""
+    from spark_rapids_ml_amd.ops.dbscan import INT32_MAX, _HipSweeps, _TorchSweeps
+    from spark_rapids_ml_amd.parallel.context import get_comm
+
+    n = 1000
+    X_np, D, eps2, half_gap, f32_err = _dbscan_blob_case(n, 20)
+    # precondition: the eps boundary is out of reach of f32 rounding
+    assert half_gap >= 5.0 * f32_err, (half_gap, f32_err)
+    near = D <= eps2
+    ref_counts = near.sum(axis=1).astype(np.int32)
+    core_np = ref_counts >= 5
+    assert ref_counts.max() >= 30 and core_np.sum() >= 100  # the data is not degenerate
+
+    dev = torch.device("cuda:0")
+    X = torch.from_numpy(X_np).to(dev)
+    row0, n_rows = 37, 700
+    hip = _HipSweeps(ext, X, row0, n_rows, get_comm(), eps2, "brute")
+    ref_backend = _TorchSweeps(X, row0, n_rows, eps2, 1)  # chunks of 125 rows
+
+    counts = hip.neighbour_counts()
+    assert counts.dtype == torch.int32
+    assert torch.equal(counts, ref_backend.neighbour_counts())
+    assert np.array_equal(counts.cpu().numpy(), ref_counts[row0 : row0 + n_rows])
+
+    labels_np = np.where(core_np, np.arange(n), INT32_MAX).astype(np.int32)
+    core = torch.from_numpy(core_np.astype(np.uint8)).to(dev)
+    labels = torch.from_numpy(labels_np).to(dev)
+    got = hip.min_core_label(core, labels)
+    ref = np.where(
+        near[row0 : row0 + n_rows] & core_np[None, :], labels_np[None, :], INT32_MAX
+    ).min(axis=1)
+    assert got.dtype == torch.int32
+    assert torch.equal(got, ref_backend.min_core_label(core, labels))
+    assert np.array_equal(got.cpu().numpy(), ref)
+
+
 @pytest.mark.parametrize("n,B", [(100000, 1), (50000, 977), (200000, 4096)])
 def test_rf_partition_matches_sort(ext, n, B):
     g = torch.Generator().manual_seed(3)
