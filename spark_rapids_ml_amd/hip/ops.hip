@@ -1476,6 +1476,222 @@ __global__ __launch_bounds__(256) void kmeans_argmin_nk_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// Split-bf16 screened assignment (ops/kmeans.py `_assign_split`).
+// The f32 GEMM of the "kn" path is bound by the f32 MFMA rate; the argmin
+// only needs dots good enough to separate the best two centres. Every value
+// is centred (x' = x - mu, mu = column mean of C: distances are translation
+// invariant) and split into bf16 hi + lo; the library bf16 GEMM (f32 out,
+// f32 accumulate) forms hi*hi + hi*lo + lo*hi, whose error is
+// <= 3*2^-18 |x'||c'| (u = 2^-9: |x - hi - lo| <= u^2|x|, the dropped lo*lo
+// and the two residuals are each <= u^2 sum|x_i c_i|). Rows whose best two
+// screened values lie within 4*eps*|x'|*max|c'| (eps = 2^-15) are decided in
+// double from the original data; every other row's screen argmin is exact.
+//
+// kmeans_split_bf16: one wave per row. S row = [hi(0..d) | 0 | lo(0..d) | 0],
+// each half dp = ceil32(d) wide, so both halves start 16-byte aligned.
+// Lanes walk groups of 8 columns: two 16-byte loads, one 16-byte store per
+// half; VEC=false (d % 4 != 0: rows are not 16-byte aligned) loads scalars.
+// ---------------------------------------------------------------------------
+
+__device__ __forceinline__ uint32_t bf16_rne_bits(float f) {
+  const uint32_t u = __float_as_uint(f);
+  return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void kmeans_split_bf16_kernel(
+    const float* __restrict__ A,    // [m, d]
+    const float* __restrict__ mu,   // [d]
+    int64_t m, int d, int dp,
+    uint16_t* __restrict__ S,       // [m, 2*dp] bf16 bits
+    float* __restrict__ a_sq) {     // [m]
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int groups = dp >> 3;
+  const int64_t wstride = (int64_t)gridDim.x * 4;
+  for (int64_t row = (int64_t)blockIdx.x * 4 + wave; row < m; row += wstride) {
+    const float* ar = A + row * (int64_t)d;
+    uint16_t* sr = S + row * (int64_t)(2 * dp);
+    float acc = 0.0f;
+    for (int g = lane; g < groups; g += 64) {
+      const int c0 = g * 8;
+      float x[8];
+      if (VEC) {
+        // d % 4 == 0: a float4 is either wholly inside the row or wholly pad
+        float4 v0 = make_float4(0.f, 0.f, 0.f, 0.f), v1 = v0;
+        if (c0 < d) {
+          const float4 a0 = *reinterpret_cast<const float4*>(ar + c0);
+          const float4 m0 = *reinterpret_cast<const float4*>(mu + c0);
+          v0 = make_float4(a0.x - m0.x, a0.y - m0.y, a0.z - m0.z, a0.w - m0.w);
+        }
+        if (c0 + 4 < d) {
+          const float4 a1 = *reinterpret_cast<const float4*>(ar + c0 + 4);
+          const float4 m1 = *reinterpret_cast<const float4*>(mu + c0 + 4);
+          v1 = make_float4(a1.x - m1.x, a1.y - m1.y, a1.z - m1.z, a1.w - m1.w);
+        }
+        x[0] = v0.x; x[1] = v0.y; x[2] = v0.z; x[3] = v0.w;
+        x[4] = v1.x; x[5] = v1.y; x[6] = v1.z; x[7] = v1.w;
+      } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+          x[e] = (c0 + e < d) ? ar[c0 + e] - mu[c0 + e] : 0.0f;
+      }
+      uint32_t hb[8], lb[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        hb[e] = bf16_rne_bits(x[e]);
+        // x - hi is exact in f32 (hi carries the top 8 significand bits)
+        lb[e] = bf16_rne_bits(x[e] - __uint_as_float(hb[e] << 16));
+        acc = fmaf(x[e], x[e], acc);
+      }
+      uint4 ho, lo;
+      ho.x = hb[0] | (hb[1] << 16); ho.y = hb[2] | (hb[3] << 16);
+      ho.z = hb[4] | (hb[5] << 16); ho.w = hb[6] | (hb[7] << 16);
+      lo.x = lb[0] | (lb[1] << 16); lo.y = lb[2] | (lb[3] << 16);
+      lo.z = lb[4] | (lb[5] << 16); lo.w = lb[6] | (lb[7] << 16);
+      *reinterpret_cast<uint4*>(sr + c0) = ho;
+      *reinterpret_cast<uint4*>(sr + dp + c0) = lo;
+    }
+    double s = (double)acc;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+    if (lane == 0) a_sq[row] = (float)s;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// kmeans_argmin_kn_screen: kmeans_argmin_kn's loop over the screened [k, m]
+// dot block, keeping best and second-best v = c_sq - 2*dot. A row whose
+// second is within margin_scale*sqrt(a_sq) of its best is appended to
+// flagged_rows (one atomic per wave) and left for kmeans_refine; every other
+// row is final here.
+// ---------------------------------------------------------------------------
+
+__global__ __launch_bounds__(256) void kmeans_argmin_kn_screen_kernel(
+    const float* __restrict__ dots,   // [k, m]
+    const float* __restrict__ a_sq,   // [m] centred |x'|^2
+    const float* __restrict__ c_sq,   // [k] centred |c'|^2
+    const float* __restrict__ margin_scale,  // [1] 4*eps*max_j|c'_j|
+    int64_t m, int k,
+    int32_t* __restrict__ labels,     // [m]
+    float* __restrict__ min_d,        // [m]
+    double* __restrict__ inertia,     // [1] accumulated
+    int32_t* __restrict__ flagged_rows,  // [m]
+    int32_t* __restrict__ n_flagged) {   // [1] accumulated
+  extern __shared__ float csq_s[];
+  for (int e = threadIdx.x; e < k; e += 256) csq_s[e] = c_sq[e];
+  __syncthreads();
+  const float ms = margin_scale[0];
+  const int lane = threadIdx.x & 63;
+  double local_sum = 0.0;
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  // i0 is block-uniform so every lane reaches the ballot below
+  for (int64_t i0 = (int64_t)blockIdx.x * 256; i0 < m; i0 += stride) {
+    const int64_t i = i0 + threadIdx.x;
+    const bool valid = i < m;
+    float best = 3.0e38f, second = 3.0e38f;
+    int bi = 0;
+    if (valid) {
+      for (int kk = 0; kk < k; ++kk) {
+        const float v = csq_s[kk] - 2.0f * dots[(int64_t)kk * m + i];
+        if (v < best) { second = best; best = v; bi = kk; }
+        else if (v < second) second = v;
+      }
+    }
+    const float asq = valid ? a_sq[i] : 0.0f;
+    const bool flag = valid && second <= best + ms * sqrtf(asq);
+    if (valid && !flag) {
+      const float d2 = fmaxf(best + asq, 0.0f);
+      labels[i] = bi;
+      min_d[i] = d2;
+      local_sum += (double)d2;
+    }
+    const unsigned long long mask = __ballot(flag);
+    if (mask != 0ull) {
+      const int leader = __ffsll((long long)mask) - 1;
+      int base = 0;
+      if (lane == leader) base = atomicAdd(n_flagged, __popcll(mask));
+      base = __shfl(base, leader, 64);
+      if (flag)
+        flagged_rows[base + __popcll(mask & ((1ull << lane) - 1ull))] = (int32_t)i;
+    }
+  }
+  __shared__ double red_s[256];
+  red_s[threadIdx.x] = local_sum;
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) {
+    if (threadIdx.x < off) red_s[threadIdx.x] += red_s[threadIdx.x + off];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) atomicAdd(inertia, red_s[0]);
+}
+
+// ---------------------------------------------------------------------------
+// kmeans_refine: one wave per flagged row, grid-stride over the device-side
+// list. Rescans the row's k screened values for its best, then decides among
+// every centre within the margin by sum((double)x - (double)c)^2 over the
+// ORIGINAL (uncentred) data; candidates are visited in ascending index and
+// replaced only on strictly smaller, so the lowest index wins a tie.
+// ---------------------------------------------------------------------------
+
+__global__ __launch_bounds__(256) void kmeans_refine_kernel(
+    const float* __restrict__ X,      // [m, d] original rows of this chunk
+    const float* __restrict__ C,      // [k, d] original centres
+    const float* __restrict__ dots,   // [k, m] screened
+    const float* __restrict__ c_sq,   // [k] centred
+    const float* __restrict__ a_sq,   // [m] centred
+    const float* __restrict__ margin_scale,  // [1]
+    const int32_t* __restrict__ flagged_rows,
+    const int32_t* __restrict__ n_flagged,
+    int64_t m, int d, int k,
+    int32_t* __restrict__ labels, float* __restrict__ min_d,
+    double* __restrict__ inertia) {
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int64_t nf = min((int64_t)n_flagged[0], m);
+  const float ms = margin_scale[0];
+  const int64_t wstride = (int64_t)gridDim.x * 4;
+  double local = 0.0;
+  for (int64_t f = (int64_t)blockIdx.x * 4 + wave; f < nf; f += wstride) {
+    const int64_t r = flagged_rows[f];
+    float best = 3.0e38f;
+    for (int j = lane; j < k; j += 64)
+      best = fminf(best, c_sq[j] - 2.0f * dots[(int64_t)j * m + r]);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) best = fminf(best, __shfl_xor(best, off, 64));
+    const float thr = best + ms * sqrtf(a_sq[r]);
+    const float* xr = X + r * (int64_t)d;
+    double bd = 1.0e300;
+    int bj = 0;
+    // j0 is wave-uniform so the ballot sees all 64 lanes
+    for (int j0 = 0; j0 < k; j0 += 64) {
+      const int j = j0 + lane;
+      const bool cand = j < k && (c_sq[j] - 2.0f * dots[(int64_t)j * m + r]) <= thr;
+      unsigned long long mask = __ballot(cand);
+      while (mask != 0ull) {
+        const int b = __ffsll((long long)mask) - 1;
+        mask &= mask - 1ull;
+        const float* cr = C + (int64_t)(j0 + b) * d;
+        double s = 0.0;
+        for (int e = lane; e < d; e += 64) {
+          const double df = (double)xr[e] - (double)cr[e];
+          s = fma(df, df, s);
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+        if (s < bd) { bd = s; bj = j0 + b; }
+      }
+    }
+    if (lane == 0) {
+      labels[r] = bj;
+      min_d[r] = (float)bd;
+      local += bd;
+    }
+  }
+  if (lane == 0 && local != 0.0) atomicAdd(inertia, local);
+}
+
+// ---------------------------------------------------------------------------
 // rf_partition: counting-sort rows by batch-local node id -> (perm, seg_off).
 // Replaces the per-batch torch sort + nonzero + gather chain (radix sort was
 // ~8% of RF fit kernel time; reference behavior: cuML's batched node trainer
@@ -2345,6 +2561,93 @@ std::vector<torch::Tensor> kmeans_argmin_nk(torch::Tensor dots, torch::Tensor x_
   return {labels, min_d, inertia};
 }
 
+std::vector<torch::Tensor> kmeans_split_bf16(torch::Tensor A, torch::Tensor mu) {
+  TORCH_CHECK(A.is_cuda() && A.dtype() == torch::kFloat32 && A.is_contiguous());
+  TORCH_CHECK(mu.is_cuda() && mu.dtype() == torch::kFloat32 && mu.is_contiguous());
+  TORCH_CHECK(A.dim() == 2 && mu.numel() == A.size(1), "mu must have one entry per column");
+  const int64_t m = A.size(0);
+  const int d = (int)A.size(1);
+  const int dp = (d + 31) / 32 * 32;
+  auto S = torch::empty({m, (int64_t)2 * dp}, A.options().dtype(torch::kBFloat16));
+  auto a_sq = torch::empty({m}, A.options());
+  if (m > 0) {
+    const unsigned grid = (unsigned)std::min<int64_t>(1 << 20, (m + 3) / 4);
+    auto* Sp = reinterpret_cast<uint16_t*>(S.data_ptr());
+    const bool aligned = ((uintptr_t)A.data_ptr() | (uintptr_t)mu.data_ptr()) % 16 == 0;
+    if (d % 4 == 0 && aligned)
+      hipLaunchKernelGGL(kmeans_split_bf16_kernel<true>, dim3(grid), dim3(256), 0,
+                         cur_stream(), A.data_ptr<float>(), mu.data_ptr<float>(), m, d,
+                         dp, Sp, a_sq.data_ptr<float>());
+    else
+      hipLaunchKernelGGL(kmeans_split_bf16_kernel<false>, dim3(grid), dim3(256), 0,
+                         cur_stream(), A.data_ptr<float>(), mu.data_ptr<float>(), m, d,
+                         dp, Sp, a_sq.data_ptr<float>());
+  }
+  return {S, a_sq};
+}
+
+std::vector<torch::Tensor> kmeans_argmin_kn_screen(torch::Tensor dots, torch::Tensor a_sq,
+                                                   torch::Tensor c_sq,
+                                                   torch::Tensor margin_scale) {
+  TORCH_CHECK(dots.is_cuda() && dots.dtype() == torch::kFloat32 && dots.is_contiguous());
+  TORCH_CHECK(a_sq.is_cuda() && a_sq.dtype() == torch::kFloat32 && a_sq.is_contiguous());
+  TORCH_CHECK(c_sq.is_cuda() && c_sq.dtype() == torch::kFloat32 && c_sq.is_contiguous());
+  TORCH_CHECK(margin_scale.is_cuda() && margin_scale.dtype() == torch::kFloat32 &&
+              margin_scale.numel() == 1);
+  const int k = (int)dots.size(0);
+  const int64_t m = dots.size(1);
+  TORCH_CHECK(a_sq.numel() == m && c_sq.numel() == k, "a_sq / c_sq do not match dots");
+  TORCH_CHECK((size_t)k * 4 <= 64 * 1024, "k too large for LDS stage");
+  TORCH_CHECK(m < (int64_t)1 << 31, "row chunk too large for int32 row ids");
+  auto iopt = dots.options().dtype(torch::kInt32);
+  auto labels = torch::empty({m}, iopt);
+  auto min_d = torch::empty({m}, dots.options());
+  auto inertia = torch::zeros({1}, dots.options().dtype(torch::kFloat64));
+  auto flagged = torch::empty({m}, iopt);
+  auto n_flagged = torch::zeros({1}, iopt);
+  if (m > 0) {
+    const unsigned grid = (unsigned)std::min<int64_t>(4096, (m + 255) / 256);
+    hipLaunchKernelGGL(kmeans_argmin_kn_screen_kernel, dim3(grid), dim3(256),
+                       (size_t)k * 4, cur_stream(), dots.data_ptr<float>(),
+                       a_sq.data_ptr<float>(), c_sq.data_ptr<float>(),
+                       margin_scale.data_ptr<float>(), m, k, labels.data_ptr<int32_t>(),
+                       min_d.data_ptr<float>(), inertia.data_ptr<double>(),
+                       flagged.data_ptr<int32_t>(), n_flagged.data_ptr<int32_t>());
+  }
+  return {labels, min_d, inertia, flagged, n_flagged};
+}
+
+void kmeans_refine(torch::Tensor X, torch::Tensor C, torch::Tensor dots,
+                   torch::Tensor c_sq, torch::Tensor a_sq, torch::Tensor margin_scale,
+                   torch::Tensor flagged_rows, torch::Tensor n_flagged,
+                   torch::Tensor labels, torch::Tensor min_d, torch::Tensor inertia) {
+  TORCH_CHECK(X.is_cuda() && X.dtype() == torch::kFloat32 && X.is_contiguous());
+  TORCH_CHECK(C.is_cuda() && C.dtype() == torch::kFloat32 && C.is_contiguous());
+  TORCH_CHECK(dots.is_cuda() && dots.dtype() == torch::kFloat32 && dots.is_contiguous());
+  TORCH_CHECK(c_sq.dtype() == torch::kFloat32 && c_sq.is_contiguous());
+  TORCH_CHECK(a_sq.dtype() == torch::kFloat32 && a_sq.is_contiguous());
+  TORCH_CHECK(margin_scale.dtype() == torch::kFloat32 && margin_scale.numel() == 1);
+  TORCH_CHECK(flagged_rows.dtype() == torch::kInt32 && flagged_rows.is_contiguous());
+  TORCH_CHECK(n_flagged.dtype() == torch::kInt32 && n_flagged.numel() == 1);
+  TORCH_CHECK(labels.dtype() == torch::kInt32 && labels.is_contiguous());
+  TORCH_CHECK(min_d.dtype() == torch::kFloat32 && min_d.is_contiguous());
+  TORCH_CHECK(inertia.dtype() == torch::kFloat64 && inertia.numel() == 1);
+  const int64_t m = X.size(0);
+  const int d = (int)X.size(1);
+  const int k = (int)C.size(0);
+  TORCH_CHECK(C.size(1) == d && dots.size(0) == k && dots.size(1) == m,
+              "X, C and dots shapes disagree");
+  TORCH_CHECK(c_sq.numel() == k && a_sq.numel() == m && flagged_rows.numel() == m &&
+              labels.numel() == m && min_d.numel() == m, "per-row / per-centre sizes disagree");
+  if (m == 0) return;
+  hipLaunchKernelGGL(kmeans_refine_kernel, dim3(1024), dim3(256), 0, cur_stream(),
+                     X.data_ptr<float>(), C.data_ptr<float>(), dots.data_ptr<float>(),
+                     c_sq.data_ptr<float>(), a_sq.data_ptr<float>(),
+                     margin_scale.data_ptr<float>(), flagged_rows.data_ptr<int32_t>(),
+                     n_flagged.data_ptr<int32_t>(), m, d, k, labels.data_ptr<int32_t>(),
+                     min_d.data_ptr<float>(), inertia.data_ptr<double>());
+}
+
 std::vector<torch::Tensor> rf_partition(torch::Tensor node_of_row, torch::Tensor lut,
                                         int64_t B) {
   TORCH_CHECK(node_of_row.is_cuda() && node_of_row.dtype() == torch::kInt64 &&
@@ -2585,6 +2888,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("kmeans_assign", &kmeans_assign, "fused MFMA distance + argmin");
   m.def("kmeans_argmin_kn", &kmeans_argmin_kn, "argmin epilogue over a [k,n] GEMM dot block");
   m.def("kmeans_argmin_nk", &kmeans_argmin_nk, "argmin epilogue over a row-major [m,k] GEMM dot block");
+  m.def("kmeans_split_bf16", &kmeans_split_bf16, "centre + split f32 rows into bf16 hi|lo halves, with |x'|^2");
+  m.def("kmeans_argmin_kn_screen", &kmeans_argmin_kn_screen, "best/second argmin over a screened [k,n] dot block; flags near-ties");
+  m.def("kmeans_refine", &kmeans_refine, "exact f64 decision for the flagged rows");
   m.def("label_accumulate", &label_accumulate, "per-center sum/count scatter");
   m.def("gram_f32", &gram_f32, "A^T A via MFMA f32");
   m.def("softmax_residual_loss", &softmax_residual_loss, "fused softmax residual + loss");

@@ -1,10 +1,16 @@
-"""KMeans ops: fused assignment (MFMA distance + argmin) + accumulation.
+"""KMeans ops: assignment (distance + argmin) + accumulation.
 
-HIP path (gfx950): `kmeans_assign` — LDS-tiled ‖x‖²+‖c‖²−2x·c with the
-−2XCᵀ term on mfma_f32_32x32x2f32, fused per-row argmin (packed 64-bit
-atomicMin) and block-reduced inertia; `label_accumulate` — vectorized
-per-center sum/count scatter. Together these are the KMeansMG Lloyd-step
-kernel family of the reference (clustering.py:381-415).
+HIP path (gfx950), large k and d >= D_MIN: `kmeans_split_bf16` centres and
+splits X and C into bf16 hi|lo halves, the library bf16 GEMM (f32 out) screens
+every (row, centre) pair at the bf16 MFMA rate, `kmeans_argmin_kn_screen`
+decides the rows it can, and the near-ties are decided as the f32 path
+decides them (`_refine_f32`) or, on request, in f64 by `kmeans_refine`
+(`_assign_split`). Otherwise the f32 library GEMM + `kmeans_argmin_kn` /
+`kmeans_argmin_nk` epilogues (`_assign_gemm`), or `kmeans_assign` — LDS-tiled
+‖x‖²+‖c‖²−2x·c on mfma_f32_32x32x2f32 with a fused per-row argmin.
+`label_accumulate` is the vectorized per-center sum/count scatter. Together
+these are the KMeansMG Lloyd-step kernel family of the reference (SURVEY.md
+§2.3b, clustering.py:381-415).
 """
 
 from __future__ import annotations
@@ -25,11 +31,12 @@ def kmeans_assign_reduce(
 ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, float]:
     """Returns (labels i32 [n], sums [k,d], counts [k], inertia).
 
-    Default GPU path: hipBLASLt GEMM for the C @ Xᵀ dot block (141 TF on the
-    1M×3000×k=1000 headline shape) + the own `kmeans_argmin_kn` epilogue
-    (one bandwidth-bound pass) + `label_accumulate`. The all-in-one MFMA
-    `kmeans_assign` kernel (84 TF, profiles/README.md ladder) stays selected
-    via SRML_KMEANS_VARIANT=fused."""
+    Default GPU path at the 1M×3000×k=1000 headline shape: the split-bf16
+    screen (`_assign_split`, 22.7 ms against 43.8 ms for the f32 GEMM path,
+    profiles/README.md) + `label_accumulate`. SRML_KMEANS_VARIANT=f32 keeps
+    the hipBLASLt f32 GEMM (141 TF) + `kmeans_argmin_kn` epilogue, =fused the
+    all-in-one MFMA `kmeans_assign` kernel (84 TF), =split forces the screen
+    below D_MIN columns, =split_f64 also decides its near-ties in f64."""
     if use_hip(X) and X.dtype == torch.float32:
         ext = hip_ops()
         X = X.contiguous()
@@ -55,18 +62,24 @@ def _assign(
     - large k: [k, n] GEMM + kmeans_argmin_kn (47.6 vs 74.5 ms at k=1000 —
       the dot block is compute-shaped there); k > 16384 no longer fits the
       epilogue's LDS and takes the fused kernel
+    - large k and d >= D_MIN: the same [k, n] block from the split-bf16
+      screen, `_assign_split` (27.4 vs 47.4 ms per step at k=1000, d=3000)
     - small k: X @ C^T tall-skinny GEMM + kmeans_argmin_nk wave-per-row
       epilogue (the fused kernel's 2-k-step pipeline never reaches steady
       state at small d, and the [k, n] skinny-m GEMM stalls: 205 / 280 ms
       vs 66 ms at k=200)"""
     n, k = X.shape[0], C.shape[0]
-    fused = os.environ.get("SRML_KMEANS_VARIANT") == "fused"
-    if fused or k * 4 > 64 * 1024 or n == 0:
+    variant = os.environ.get("SRML_KMEANS_VARIANT")
+    if variant == "fused" or k * 4 > 64 * 1024 or n == 0:
         labels, _min_d, inertia = ext.kmeans_assign(
             X, C.contiguous(), x_sq.contiguous()
         )
         return labels, inertia
-    return _assign_gemm(ext, X, C, x_sq, n, k, layout="kn" if k >= 384 else "nk")
+    if k < 384:
+        return _assign_gemm(ext, X, C, x_sq, n, k, layout="nk")
+    if _use_split(variant, X.shape[1]):
+        return _assign_split(ext, X, C, x_sq, n, k, exact=variant == "split_f64")
+    return _assign_gemm(ext, X, C, x_sq, n, k, layout="kn")
 
 
 def _assign_gemm(
@@ -100,6 +113,134 @@ def _assign_gemm(
         e = min(n, s + rchunk)
         dv = dots_of(s, e, out=dots if e - s == rchunk else dots_buf(e - s))
         lb, _md, it = argmin(dv, x_sq[s:e].contiguous(), c_sq)
+        labels[s:e] = lb
+        inertia += it
+    return labels, inertia
+
+
+# Split-bf16 screen (see `_assign_split`). SPLIT_EPS bounds one screened dot's
+# error relative to |x'||c'|: the three-term split is within 3*2^-18, the rest
+# (~2.7x) is left for the f32 accumulation.
+SPLIT_EPS = 2.0 ** -15
+# Measured with tools/time_assign_split.py at 1M rows, k=1000 (tables in
+# profiles/README.md). D_MIN: the screen loses at d=256 (5.29 vs 4.95 ms) and
+# wins at d=512 (6.55 vs 8.22 ms); below that the split pass and the second
+# pass over the dot block outweigh the cheaper GEMM. F_MAX: the screen still
+# wins 1.48x at 12.8 % flagged and breaks even near 40 % (`_refine_f32` costs
+# about 50 ns per flagged row); a fallback costs the discarded screen of one
+# chunk on top of the f32 path, so the cut-off sits below the break-even.
+D_MIN = 512
+F_MAX = 0.25
+
+
+def _use_split(variant: Optional[str], d: int) -> bool:
+    """SRML_KMEANS_VARIANT=f32 forces the f32 GEMM, =split and =split_f64
+    (near-ties decided in f64) force the screen; unset takes the screen from
+    D_MIN columns on."""
+    if variant == "f32":
+        return False
+    return variant in ("split", "split_f64") or d >= D_MIN
+
+
+def _split_dots(
+    Ch2: torch.Tensor, Cl: torch.Tensor, SX: torch.Tensor, dp: int, out: torch.Tensor
+) -> torch.Tensor:
+    """out[k, m] = Ch·Xh + Ch·Xl + Cl·Xh from the split operands: bf16 in, f32
+    accumulate, f32 out (a bf16 result would discard what the split buys).
+    [Ch|Ch] @ [Xh|Xl]ᵀ, then += Cl @ Xhᵀ on the strided hi half (no copy)."""
+    torch.mm(Ch2, SX.T, out_dtype=torch.float32, out=out)
+    return torch.addmm(out, Cl, SX[:, :dp].T, out_dtype=torch.float32, out=out)
+
+
+def _fallback_f32(
+    ext, X: torch.Tensor, C: torch.Tensor, x_sq: torch.Tensor, n: int, k: int
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The screen separated too few rows (duplicate / degenerate centres):
+    this call runs the f32 GEMM path instead."""
+    return _assign_gemm(ext, X, C, x_sq, n, k, layout="kn")
+
+
+def _refine_f32(
+    ext, Xc: torch.Tensor, C: torch.Tensor, x_sqc: torch.Tensor, rows: torch.Tensor
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(labels, inertia) of the listed rows of Xc by the f32 path's own
+    arithmetic: the f32 library GEMM on the gathered rows + `kmeans_argmin_kn`.
+
+    A near-tie is decided by rounding, so only the same rounding reproduces
+    what the f32 path assigns. Per element the library GEMM walks K in one
+    order whatever the shape, except in the few tiles it splits along K:
+    gathered rows, padded to a multiple of 256 with repeats of the first one,
+    get 97-100 % of their dots bit-equal to the full GEMM's (measured,
+    profiles/README.md), against 3 % unpadded at 64 rows or fewer."""
+    nf = rows.numel()
+    pad = -nf % 256
+    idx = torch.cat([rows, rows[:1].expand(pad)]) if pad else rows
+    dots = torch.mm(C, Xc[idx].T)
+    c_sq = (C * C).sum(dim=1).contiguous()
+    lf, md, _it = ext.kmeans_argmin_kn(dots, x_sqc[idx].contiguous(), c_sq)
+    return lf[:nf], md[:nf].double().sum()
+
+
+def _assign_split(
+    ext, X: torch.Tensor, C: torch.Tensor, x_sq: torch.Tensor, n: int, k: int,
+    max_bytes: int = 8 << 30, exact: bool = False,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Screened assignment: the [k, chunk] dot block comes from the bf16 MFMA
+    rate instead of the f32 one, and only near-ties are decided again.
+
+    X and C are centred by the column mean of C (distances are translation
+    invariant; without it data far from the origin flags every row) and split
+    by `kmeans_split_bf16` into bf16 hi|lo halves; `_split_dots` forms the
+    three-term product, each dot within SPLIT_EPS·|x'||c'| of exact.
+    `kmeans_argmin_kn_screen` finalises every row whose best two values are
+    further apart than 4·SPLIT_EPS·|x'|·max|c'| — there the screen's argmin is
+    the exact one and, its rounding being far smaller than that margin, the f32
+    path's too — and lists the others. Those are
+    decided by `_refine_f32`, as the f32 path decides them, so a fit takes the
+    course it took before; with `exact` (SRML_KMEANS_VARIANT=split_f64)
+    `kmeans_refine` decides them in f64 from the original X and C instead,
+    and labels equal the f64 argmin wherever the bound holds. Rows are chunked
+    so split buffer + dot block stay under `max_bytes`. If more than F_MAX of
+    a chunk is listed, the screen is discarded and `_fallback_f32` runs the
+    call."""
+    Cc = C.contiguous()
+    mu = Cc.mean(dim=0)
+    SC, c_sq = ext.kmeans_split_bf16(Cc, mu)
+    dp = SC.shape[1] // 2
+    Ch2 = torch.cat([SC[:, :dp], SC[:, :dp]], dim=1)
+    Cl = SC[:, dp:].contiguous()
+    margin = ((4.0 * SPLIT_EPS) * c_sq.max().sqrt()).reshape(1)
+
+    rchunk = max(256, int(max_bytes // (k * 4 + 4 * dp)))
+    single = rchunk >= n
+    labels = None if single else torch.empty(n, dtype=torch.int32, device=X.device)
+    inertia = torch.zeros(1, dtype=torch.float64, device=X.device)
+    dots = torch.empty((k, min(n, rchunk)), dtype=torch.float32, device=X.device)
+    for s in range(0, n, rchunk):
+        e = min(n, s + rchunk)
+        Xc = X[s:e]
+        SX, a_sq = ext.kmeans_split_bf16(Xc, mu)
+        if e - s != dots.shape[1]:
+            dots = torch.empty((k, e - s), dtype=torch.float32, device=X.device)
+        _split_dots(Ch2, Cl, SX, dp, dots)
+        del SX  # only the GEMMs read it; the next chunk's split reuses the block
+        lb, md, it, flagged, n_flagged = ext.kmeans_argmin_kn_screen(
+            dots, a_sq, c_sq, margin
+        )
+        nf = int(n_flagged.item())
+        if nf > F_MAX * (e - s):
+            return _fallback_f32(ext, X, C, x_sq, n, k)
+        if nf and exact:
+            ext.kmeans_refine(
+                Xc, Cc, dots, c_sq, a_sq, margin, flagged, n_flagged, lb, md, it
+            )
+        elif nf:
+            rows = flagged[:nf].long()
+            lf, itf = _refine_f32(ext, Xc, Cc, x_sq[s:e], rows)
+            lb[rows] = lf
+            it += itf
+        if single:
+            return lb, it
         labels[s:e] = lb
         inertia += it
     return labels, inertia
