@@ -19,6 +19,7 @@
 // unit-stride along a row.
 
 #include <torch/extension.h>
+#include <c10/hip/HIPException.h>
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_runtime.h>
 
@@ -2235,6 +2236,7 @@ torch::Tensor dbscan_sweep(torch::Tensor X, torch::Tensor x_sq, int64_t row0,
                      pruned ? tile_idx.data_ptr<int32_t>() : nullptr,
                      pruned ? tile_off.data_ptr<int32_t>() : nullptr,
                      out.data_ptr<int32_t>());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   return out;
 }
 
@@ -2270,6 +2272,7 @@ torch::Tensor umap_sgd(torch::Tensor emb, torch::Tensor tail_emb,
       default: UMAP_LAUNCH(4); break;
     }
 #undef UMAP_LAUNCH
+    C10_HIP_KERNEL_LAUNCH_CHECK();
   }
   return emb;
 }
@@ -2310,6 +2313,7 @@ std::vector<torch::Tensor> kmeans_assign(torch::Tensor X, torch::Tensor C,
                        c_sq.data_ptr<float>(), (int)n, d, k,
                        labels.data_ptr<int32_t>(), min_dists.data_ptr<float>(),
                        inertia.data_ptr<double>());
+    C10_HIP_KERNEL_LAUNCH_CHECK();
   }
   return {labels, min_dists, inertia};
 }
@@ -2331,6 +2335,7 @@ std::vector<torch::Tensor> label_accumulate(torch::Tensor X, torch::Tensor label
                        labels.data_ptr<int32_t>(), n, d, (int)k,
                        rows_per_block, sums.data_ptr<float>(),
                        counts.data_ptr<float>());
+    C10_HIP_KERNEL_LAUNCH_CHECK();
     return {sums, counts};
   }
   {
@@ -2343,6 +2348,7 @@ std::vector<torch::Tensor> label_accumulate(torch::Tensor X, torch::Tensor label
                        cur_stream(), X.data_ptr<float>(), perm.data_ptr<int64_t>(),
                        seg_off.data_ptr<int64_t>(), d, sums.data_ptr<float>(),
                        counts.data_ptr<float>());
+    C10_HIP_KERNEL_LAUNCH_CHECK();
   }
   return {sums, counts};
 }
@@ -2359,9 +2365,11 @@ torch::Tensor gram_f32(torch::Tensor A) {
     dim3 grid((unsigned)(tri * split));
     hipLaunchKernelGGL(gram_kernel, grid, dim3(256), 0, cur_stream(),
                        A.data_ptr<float>(), n, d, nb, split, out.data_ptr<float>());
+    C10_HIP_KERNEL_LAUNCH_CHECK();
     int mgrid = (int)std::min<int64_t>(2048, ((int64_t)d * d + 255) / 256);
     hipLaunchKernelGGL(gram_mirror_kernel, dim3(mgrid), dim3(256), 0, cur_stream(),
                        out.data_ptr<float>(), d);
+    C10_HIP_KERNEL_LAUNCH_CHECK();
   }
   return out;
 }
@@ -2380,11 +2388,13 @@ std::vector<torch::Tensor> knn_select(torch::Tensor Q, torch::Tensor I, int64_t 
   int isplit = std::max(1, std::min((ni + KN_IB - 1) / KN_IB, 512 / std::max(1, qblocks)));
   auto dist = torch::empty({nq, (int64_t)isplit, k}, Q.options());
   auto idx = torch::empty({nq, (int64_t)isplit, k}, Q.options().dtype(torch::kInt32));
-  if (nq > 0 && ni > 0)
+  if (nq > 0 && ni > 0) {
     hipLaunchKernelGGL(knn_select_kernel, dim3((unsigned)(qblocks * isplit)), dim3(256),
                        0, cur_stream(), Q.data_ptr<float>(), I.data_ptr<float>(),
                        q_sq.data_ptr<float>(), i_sq.data_ptr<float>(), nq, ni, d,
                        (int)k, isplit, dist.data_ptr<float>(), idx.data_ptr<int32_t>());
+    C10_HIP_KERNEL_LAUNCH_CHECK();
+  }
   // merge partial top-k across item splits
   auto dflat = dist.view({nq, (int64_t)isplit * k});
   auto iflat = idx.view({nq, (int64_t)isplit * k});
@@ -2409,6 +2419,7 @@ std::vector<torch::Tensor> softmax_residual_loss(torch::Tensor scores, torch::Te
     hipLaunchKernelGGL(softmax_residual_kernel, dim3(grid), dim3(256), 0, cur_stream(),
                        scores.data_ptr<float>(), y.data_ptr<int64_t>(), n, C,
                        resid.data_ptr<float>(), loss.data_ptr<float>());
+    C10_HIP_KERNEL_LAUNCH_CHECK();
   }
   return {resid, loss.squeeze(0)};
 }
@@ -2456,6 +2467,7 @@ torch::Tensor rf_histogram(torch::Tensor Xb, torch::Tensor perm, torch::Tensor s
                      d, mf, (int)f0, (int)FC, (int)n_bins, C, split,
                      y_inv_scale, y_scale,
                      out.data_ptr<float>());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   return out;
 }
 
@@ -2498,6 +2510,7 @@ torch::Tensor rf_histogram_fw(torch::Tensor Xrm, torch::Tensor perm, torch::Tens
                      d, mf, (int)f0, (int)FC, (int)n_bins, C, split,
                      y_inv_scale, y_scale,
                      out.data_ptr<float>());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   return out;
 }
 
@@ -2515,12 +2528,14 @@ std::vector<torch::Tensor> rf_best_split(torch::Tensor H, int64_t min_leaf,
   auto bin = torch::empty({B}, H.options().dtype(torch::kInt32));
   auto lval = torch::empty({B, C}, H.options());
   auto rval = torch::empty({B, C}, H.options());
-  if (B > 0)
+  if (B > 0) {
     hipLaunchKernelGGL(rf_best_split_kernel, dim3((unsigned)B), dim3(256), 0,
                        cur_stream(), H.data_ptr<float>(), F, nb, C,
                        (int)min_leaf, classif ? 1 : 0, gain.data_ptr<float>(),
                        feat.data_ptr<int32_t>(), bin.data_ptr<int32_t>(),
                        lval.data_ptr<float>(), rval.data_ptr<float>());
+    C10_HIP_KERNEL_LAUNCH_CHECK();
+  }
   return {gain, feat, bin, lval, rval};
 }
 
@@ -2539,6 +2554,7 @@ std::vector<torch::Tensor> kmeans_argmin_kn(torch::Tensor dots, torch::Tensor x_
                      cur_stream(), dots.data_ptr<float>(), x_sq.data_ptr<float>(),
                      c_sq.data_ptr<float>(), n, k, labels.data_ptr<int32_t>(),
                      min_d.data_ptr<float>(), inertia.data_ptr<double>());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   return {labels, min_d, inertia};
 }
 
@@ -2557,6 +2573,7 @@ std::vector<torch::Tensor> kmeans_argmin_nk(torch::Tensor dots, torch::Tensor x_
                        cur_stream(), dots.data_ptr<float>(), x_sq.data_ptr<float>(),
                        c_sq.data_ptr<float>(), m, k, labels.data_ptr<int32_t>(),
                        min_d.data_ptr<float>(), inertia.data_ptr<double>());
+    C10_HIP_KERNEL_LAUNCH_CHECK();
   }
   return {labels, min_d, inertia};
 }
@@ -2582,6 +2599,7 @@ std::vector<torch::Tensor> kmeans_split_bf16(torch::Tensor A, torch::Tensor mu) 
       hipLaunchKernelGGL(kmeans_split_bf16_kernel<false>, dim3(grid), dim3(256), 0,
                          cur_stream(), A.data_ptr<float>(), mu.data_ptr<float>(), m, d,
                          dp, Sp, a_sq.data_ptr<float>());
+    C10_HIP_KERNEL_LAUNCH_CHECK();
   }
   return {S, a_sq};
 }
@@ -2613,6 +2631,7 @@ std::vector<torch::Tensor> kmeans_argmin_kn_screen(torch::Tensor dots, torch::Te
                        margin_scale.data_ptr<float>(), m, k, labels.data_ptr<int32_t>(),
                        min_d.data_ptr<float>(), inertia.data_ptr<double>(),
                        flagged.data_ptr<int32_t>(), n_flagged.data_ptr<int32_t>());
+    C10_HIP_KERNEL_LAUNCH_CHECK();
   }
   return {labels, min_d, inertia, flagged, n_flagged};
 }
@@ -2646,6 +2665,7 @@ void kmeans_refine(torch::Tensor X, torch::Tensor C, torch::Tensor dots,
                      margin_scale.data_ptr<float>(), flagged_rows.data_ptr<int32_t>(),
                      n_flagged.data_ptr<int32_t>(), m, d, k, labels.data_ptr<int32_t>(),
                      min_d.data_ptr<float>(), inertia.data_ptr<double>());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
 }
 
 std::vector<torch::Tensor> rf_partition(torch::Tensor node_of_row, torch::Tensor lut,
@@ -2661,6 +2681,7 @@ std::vector<torch::Tensor> rf_partition(torch::Tensor node_of_row, torch::Tensor
   hipLaunchKernelGGL(rf_node_count_kernel, dim3(grid), dim3(256), lds1, cur_stream(),
                      node_of_row.data_ptr<int64_t>(), lut.data_ptr<int64_t>(), n, (int)B,
                      counts.data_ptr<int32_t>());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   auto seg_off = torch::zeros({B + 1}, node_of_row.options().dtype(torch::kInt64));
   seg_off.narrow(0, 1, B).copy_(torch::cumsum(counts, 0));
   auto cursor = seg_off.narrow(0, 0, B).to(torch::kInt32).contiguous();
@@ -2669,6 +2690,7 @@ std::vector<torch::Tensor> rf_partition(torch::Tensor node_of_row, torch::Tensor
   hipLaunchKernelGGL(rf_partition_scatter_kernel, dim3(grid), dim3(256), lds2, cur_stream(),
                      node_of_row.data_ptr<int64_t>(), lut.data_ptr<int64_t>(), n, (int)B,
                      cursor.data_ptr<int32_t>(), perm.data_ptr<int64_t>());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   return {perm, seg_off};
 }
 
@@ -2692,6 +2714,7 @@ void rf_reroute(torch::Tensor node_of_row, torch::Tensor lut2, torch::Tensor sfe
                      Xb.data_ptr<uint8_t>(),
                      has_sample ? sample.data_ptr<int32_t>() : nullptr, n_phys,
                      vn, d);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
 }
 
 void knn_merge_topk(torch::Tensor G, torch::Tensor q_sq, torch::Tensor i_sq,
@@ -2708,6 +2731,7 @@ void knn_merge_topk(torch::Tensor G, torch::Tensor q_sq, torch::Tensor i_sq,
                      cur_stream(), G.data_ptr<float>(), q_sq.data_ptr<float>(),
                      i_sq.data_ptr<float>(), nq, c, base, best_d.data_ptr<float>(),
                      best_i.data_ptr<int64_t>());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
 }
 
 torch::Tensor gather_dists(torch::Tensor A, torch::Tensor B, torch::Tensor cand) {
@@ -2720,10 +2744,12 @@ torch::Tensor gather_dists(torch::Tensor A, torch::Tensor B, torch::Tensor cand)
   TORCH_CHECK((int)B.size(1) == d && A.size(0) == r);
   TORCH_CHECK(d <= GD_DMAX, "gather_dists supports d <= 2048");
   auto out = torch::empty({r, m}, A.options());
-  if (r > 0 && m > 0)
+  if (r > 0 && m > 0) {
     hipLaunchKernelGGL(gather_dists_kernel, dim3((unsigned)((r + 3) / 4)), dim3(256), 0,
                        cur_stream(), A.data_ptr<float>(), B.data_ptr<float>(),
                        cand.data_ptr<int64_t>(), r, m, d, out.data_ptr<float>());
+    C10_HIP_KERNEL_LAUNCH_CHECK();
+  }
   return out;
 }
 
@@ -2742,6 +2768,7 @@ static void ivf_scan_topk_launch(int64_t mode, unsigned grid, const float* Q,
     hipLaunchKernelGGL((ivf_scan_topk_kernel<NSEG, 1>), dim3(grid), dim3(256), 0,
                        cur_stream(), Q, Xs, list_off, pair_q, pair_list, pair_out,
                        P, nq, n, nlist, n_out, d, k, part_key, part_pos);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
 }
 
 std::vector<torch::Tensor> ivf_scan_topk(torch::Tensor Q, torch::Tensor Xs,
@@ -2808,6 +2835,7 @@ torch::Tensor fil_predict(torch::Tensor X, torch::Tensor feat, torch::Tensor thr
                        right.data_ptr<int32_t>(), value.data_ptr<float>(),
                        roots.data_ptr<int64_t>(), n, d, T, vw, classif ? 1 : 0,
                        out.data_ptr<float>());
+    C10_HIP_KERNEL_LAUNCH_CHECK();
   }
   return out;
 }
@@ -2826,11 +2854,13 @@ torch::Tensor csr_fwd(torch::Tensor indptr, torch::Tensor indices, torch::Tensor
                        indptr.data_ptr<int32_t>(), indices.data_ptr<int32_t>(),
                        vals.data_ptr<float>(), WT.data_ptr<float>(), n, C,
                        scores.data_ptr<float>());
+    C10_HIP_KERNEL_LAUNCH_CHECK();
   } else {
     hipLaunchKernelGGL(csr_fwd_kernel<int64_t>, dim3(grid), dim3(256), 0, cur_stream(),
                        indptr.data_ptr<int64_t>(), indices.data_ptr<int64_t>(),
                        vals.data_ptr<float>(), WT.data_ptr<float>(), n, C,
                        scores.data_ptr<float>());
+    C10_HIP_KERNEL_LAUNCH_CHECK();
   }
   return scores;
 }
@@ -2852,11 +2882,13 @@ torch::Tensor csr_grad(torch::Tensor indptr, torch::Tensor indices, torch::Tenso
                        indptr.data_ptr<int32_t>(), indices.data_ptr<int32_t>(),
                        vals.data_ptr<float>(), resid.data_ptr<float>(), n, d, C, use_lds,
                        grad.data_ptr<float>());
+    C10_HIP_KERNEL_LAUNCH_CHECK();
   } else {
     hipLaunchKernelGGL(csr_grad_kernel<int64_t>, dim3(grid), dim3(256), lds, cur_stream(),
                        indptr.data_ptr<int64_t>(), indices.data_ptr<int64_t>(),
                        vals.data_ptr<float>(), resid.data_ptr<float>(), n, d, C, use_lds,
                        grad.data_ptr<float>());
+    C10_HIP_KERNEL_LAUNCH_CHECK();
   }
   return grad;
 }
@@ -2872,10 +2904,12 @@ torch::Tensor csr_col_moments(torch::Tensor indices, torch::Tensor vals, int64_t
     hipLaunchKernelGGL(csr_col_moments_kernel<int32_t>, dim3(grid), dim3(256), lds,
                        cur_stream(), indices.data_ptr<int32_t>(),
                        vals.data_ptr<float>(), nnz, d, out.data_ptr<double>());
+    C10_HIP_KERNEL_LAUNCH_CHECK();
   } else {
     hipLaunchKernelGGL(csr_col_moments_kernel<int64_t>, dim3(grid), dim3(256), lds,
                        cur_stream(), indices.data_ptr<int64_t>(),
                        vals.data_ptr<float>(), nnz, d, out.data_ptr<double>());
+    C10_HIP_KERNEL_LAUNCH_CHECK();
   }
   return out;
 }
