@@ -545,6 +545,127 @@ __global__ __launch_bounds__(256) void segment_sum_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// segment_sum_inertia: segment_sum that also returns sum_i |x_i - c_label(i)|^2.
+// A block streams the rows of ONE label over its column stripe, so it keeps
+// that centre's stripe in registers and squares (x - c) beside the sum: no
+// further pass over X. The squares are summed in f32 over one 4-row group of
+// the thread's columns (64 terms), then added into a double; one f64 atomic
+// per block. The direct difference has no |x|^2 + |c|^2 - 2x.c cancellation.
+// Per column the rows are added in segment_sum's order and grouping, so sums
+// and counts equal label_accumulate's. VEC (d % 4 == 0, 16-byte aligned
+// bases): each lane loads float4s, 4 per row instead of 16 scalars.
+// ---------------------------------------------------------------------------
+
+constexpr bool LA_VEC_DEFAULT = true;
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void segment_sum_inertia_kernel(
+    const float* __restrict__ X, const int64_t* __restrict__ perm,
+    const int64_t* __restrict__ seg_off, const float* __restrict__ C, int d,
+    float* __restrict__ sums, float* __restrict__ counts,
+    double* __restrict__ inertia) {
+  constexpr int W = VEC ? 4 : 1;      // columns per load
+  constexpr int NQ = LA_COLS / W;     // loads per thread and row
+  const int lab = blockIdx.x / LA_SPLIT;
+  const int split = blockIdx.x % LA_SPLIT;
+  const int64_t s0 = seg_off[lab], e0 = seg_off[lab + 1];
+  const int64_t len = e0 - s0;
+  if (len == 0) return;
+  const int64_t chunk = (len + LA_SPLIT - 1) / LA_SPLIT;
+  const int64_t rs = s0 + split * chunk;
+  const int64_t re = min(e0, rs + chunk);
+  if (rs >= re) return;  // block-uniform: no barrier is skipped by part of a block
+  if (split == 0 && threadIdx.x == 0) counts[lab] = (float)len;
+
+  auto ld = [](const float* p, float* out) {
+    if constexpr (VEC) {
+      const float4 v = *reinterpret_cast<const float4*>(p);
+      out[0] = v.x; out[1] = v.y; out[2] = v.z; out[3] = v.w;
+    } else {
+      out[0] = *p;
+    }
+  };
+
+  const float* crow = C + (int64_t)lab * d;
+  double local = 0.0;
+  for (int cb = 0; cb < d; cb += blockDim.x * LA_COLS) {
+    float acc[LA_COLS], cen[LA_COLS];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      const int c = cb + (q * blockDim.x + threadIdx.x) * W;
+#pragma unroll
+      for (int w = 0; w < W; ++w) { acc[q * W + w] = 0.0f; cen[q * W + w] = 0.0f; }
+      if (c < d) ld(crow + c, cen + q * W);  // VEC: d % 4 == 0, all 4 inside
+    }
+    int64_t r = rs;
+    for (; r + 4 <= re; r += 4) {  // 4 rows in flight for latency hiding
+      const float* row0 = X + perm[r] * (int64_t)d;
+      const float* row1 = X + perm[r + 1] * (int64_t)d;
+      const float* row2 = X + perm[r + 2] * (int64_t)d;
+      const float* row3 = X + perm[r + 3] * (int64_t)d;
+      float part = 0.0f;
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) {
+        const int c = cb + (q * blockDim.x + threadIdx.x) * W;
+        if (c < d) {
+          float x0[W], x1[W], x2[W], x3[W];
+          ld(row0 + c, x0); ld(row1 + c, x1); ld(row2 + c, x2); ld(row3 + c, x3);
+#pragma unroll
+          for (int w = 0; w < W; ++w) {
+            const float ce = cen[q * W + w];
+            acc[q * W + w] += x0[w] + x1[w] + x2[w] + x3[w];
+            const float f0 = x0[w] - ce, f1 = x1[w] - ce, f2 = x2[w] - ce, f3 = x3[w] - ce;
+            part = fmaf(f0, f0, part); part = fmaf(f1, f1, part);
+            part = fmaf(f2, f2, part); part = fmaf(f3, f3, part);
+          }
+        }
+      }
+      local += (double)part;
+    }
+    for (; r < re; ++r) {
+      const float* row = X + perm[r] * (int64_t)d;
+      float part = 0.0f;
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) {
+        const int c = cb + (q * blockDim.x + threadIdx.x) * W;
+        if (c < d) {
+          float x0[W];
+          ld(row + c, x0);
+#pragma unroll
+          for (int w = 0; w < W; ++w) {
+            acc[q * W + w] += x0[w];
+            const float f0 = x0[w] - cen[q * W + w];
+            part = fmaf(f0, f0, part);
+          }
+        }
+      }
+      local += (double)part;
+    }
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      const int c = cb + (q * blockDim.x + threadIdx.x) * W;
+      if (c < d) {
+#pragma unroll
+        for (int w = 0; w < W; ++w) {
+          if (LA_SPLIT > 1)
+            atomicAdd(&sums[(int64_t)lab * d + c + w], acc[q * W + w]);
+          else
+            sums[(int64_t)lab * d + c + w] = acc[q * W + w];
+        }
+      }
+    }
+  }
+  __shared__ double red_s[256];
+  red_s[threadIdx.x] = local;
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) {
+    if (threadIdx.x < off) red_s[threadIdx.x] += red_s[threadIdx.x + off];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) atomicAdd(inertia, red_s[0]);
+}
+
+// ---------------------------------------------------------------------------
 // label_accumulate_lds: direct one-pass scatter for small k*d. Each block
 // owns an LDS-private [k,d] f32 accumulator (+ k counts), streams its row
 // range in NATURAL order — X read once, coalesced, no sort and no permuted
@@ -1492,6 +1613,8 @@ __global__ __launch_bounds__(256) void kmeans_argmin_nk_kernel(
 // each half dp = ceil32(d) wide, so both halves start 16-byte aligned.
 // Lanes walk groups of 8 columns: two 16-byte loads, one 16-byte store per
 // half; VEC=false (d % 4 != 0: rows are not 16-byte aligned) loads scalars.
+// LO=false (kmeans_split_bf16_hi) neither computes nor stores the lo half:
+// S row = [hi(0..d) | 0], dp wide, same hi bits and same a_sq.
 // ---------------------------------------------------------------------------
 
 __device__ __forceinline__ uint32_t bf16_rne_bits(float f) {
@@ -1499,12 +1622,12 @@ __device__ __forceinline__ uint32_t bf16_rne_bits(float f) {
   return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
 }
 
-template <bool VEC>
+template <bool VEC, bool LO>
 __global__ __launch_bounds__(256) void kmeans_split_bf16_kernel(
     const float* __restrict__ A,    // [m, d]
     const float* __restrict__ mu,   // [d]
     int64_t m, int d, int dp,
-    uint16_t* __restrict__ S,       // [m, 2*dp] bf16 bits
+    uint16_t* __restrict__ S,       // [m, 2*dp] bf16 bits; [m, dp] without LO
     float* __restrict__ a_sq) {     // [m]
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
@@ -1512,7 +1635,7 @@ __global__ __launch_bounds__(256) void kmeans_split_bf16_kernel(
   const int64_t wstride = (int64_t)gridDim.x * 4;
   for (int64_t row = (int64_t)blockIdx.x * 4 + wave; row < m; row += wstride) {
     const float* ar = A + row * (int64_t)d;
-    uint16_t* sr = S + row * (int64_t)(2 * dp);
+    uint16_t* sr = S + row * (int64_t)(LO ? 2 * dp : dp);
     float acc = 0.0f;
     for (int g = lane; g < groups; g += 64) {
       const int c0 = g * 8;
@@ -1542,16 +1665,19 @@ __global__ __launch_bounds__(256) void kmeans_split_bf16_kernel(
       for (int e = 0; e < 8; ++e) {
         hb[e] = bf16_rne_bits(x[e]);
         // x - hi is exact in f32 (hi carries the top 8 significand bits)
-        lb[e] = bf16_rne_bits(x[e] - __uint_as_float(hb[e] << 16));
+        if (LO) lb[e] = bf16_rne_bits(x[e] - __uint_as_float(hb[e] << 16));
         acc = fmaf(x[e], x[e], acc);
       }
-      uint4 ho, lo;
+      uint4 ho;
       ho.x = hb[0] | (hb[1] << 16); ho.y = hb[2] | (hb[3] << 16);
       ho.z = hb[4] | (hb[5] << 16); ho.w = hb[6] | (hb[7] << 16);
-      lo.x = lb[0] | (lb[1] << 16); lo.y = lb[2] | (lb[3] << 16);
-      lo.z = lb[4] | (lb[5] << 16); lo.w = lb[6] | (lb[7] << 16);
       *reinterpret_cast<uint4*>(sr + c0) = ho;
-      *reinterpret_cast<uint4*>(sr + dp + c0) = lo;
+      if (LO) {
+        uint4 lo;
+        lo.x = lb[0] | (lb[1] << 16); lo.y = lb[2] | (lb[3] << 16);
+        lo.z = lb[4] | (lb[5] << 16); lo.w = lb[6] | (lb[7] << 16);
+        *reinterpret_cast<uint4*>(sr + dp + c0) = lo;
+      }
     }
     double s = (double)acc;
 #pragma unroll
@@ -1565,8 +1691,13 @@ __global__ __launch_bounds__(256) void kmeans_split_bf16_kernel(
 // dot block, keeping best and second-best v = c_sq - 2*dot. A row whose
 // second is within margin_scale*sqrt(a_sq) of its best is appended to
 // flagged_rows (one atomic per wave) and left for kmeans_refine; every other
-// row is final here.
+// row is final here. One thread per row; the loop over centres is batched
+// and branch-free so the loads of a batch are in flight together: 5.7 TB/s on
+// the 4 GB block of 1M rows x k=1000, against 2.4 TB/s for one dependent
+// compare-and-branch per load (profiles/README.md "Prepared X").
 // ---------------------------------------------------------------------------
+
+constexpr int SCREEN_BATCH = 8;  // centres loaded per row before any is used
 
 __global__ __launch_bounds__(256) void kmeans_argmin_kn_screen_kernel(
     const float* __restrict__ dots,   // [k, m]
@@ -1593,10 +1724,31 @@ __global__ __launch_bounds__(256) void kmeans_argmin_kn_screen_kernel(
     float best = 3.0e38f, second = 3.0e38f;
     int bi = 0;
     if (valid) {
-      for (int kk = 0; kk < k; ++kk) {
-        const float v = csq_s[kk] - 2.0f * dots[(int64_t)kk * m + i];
-        if (v < best) { second = best; best = v; bi = kk; }
-        else if (v < second) second = v;
+      // SCREEN_BATCH independent loads are issued before the first is used,
+      // and the update is select-only: v < best shifts best into second,
+      // otherwise second = min(second, v) (an equal v keeps the lower index
+      // and lands in second, as the branchy form did).
+      const float* col = dots + i;
+      int kk = 0;
+      for (; kk + SCREEN_BATCH <= k; kk += SCREEN_BATCH) {
+        float dv[SCREEN_BATCH];
+#pragma unroll
+        for (int u = 0; u < SCREEN_BATCH; ++u) dv[u] = col[(int64_t)(kk + u) * m];
+#pragma unroll
+        for (int u = 0; u < SCREEN_BATCH; ++u) {
+          const float v = csq_s[kk + u] - 2.0f * dv[u];
+          const bool lt = v < best;
+          second = lt ? best : fminf(second, v);
+          bi = lt ? kk + u : bi;
+          best = lt ? v : best;
+        }
+      }
+      for (; kk < k; ++kk) {
+        const float v = csq_s[kk] - 2.0f * col[(int64_t)kk * m];
+        const bool lt = v < best;
+        second = lt ? best : fminf(second, v);
+        bi = lt ? kk : bi;
+        best = lt ? v : best;
       }
     }
     const float asq = valid ? a_sq[i] : 0.0f;
@@ -2353,6 +2505,45 @@ std::vector<torch::Tensor> label_accumulate(torch::Tensor X, torch::Tensor label
   return {sums, counts};
 }
 
+// (sums [k,d], counts [k], inertia f64 [1]) on the sorted segment path, k and
+// the centres taken from C. `vec` selects the 16-byte row loads where the
+// layout allows them.
+std::vector<torch::Tensor> label_accumulate_inertia(torch::Tensor X, torch::Tensor labels,
+                                                    torch::Tensor C, bool vec) {
+  TORCH_CHECK(X.is_cuda() && labels.is_cuda() && C.is_cuda(), "device tensors required");
+  TORCH_CHECK(X.dtype() == torch::kFloat32 && X.is_contiguous() && X.dim() == 2);
+  TORCH_CHECK(C.dtype() == torch::kFloat32 && C.is_contiguous() && C.dim() == 2);
+  TORCH_CHECK(C.size(1) == X.size(1), "X and C column counts disagree");
+  TORCH_CHECK(labels.numel() == X.size(0), "one label per row");
+  const int64_t n = X.size(0);
+  const int64_t k = C.size(0);
+  const int d = (int)X.size(1);
+  auto sums = torch::zeros({k, d}, X.options());
+  auto counts = torch::zeros({k}, X.options());
+  auto inertia = torch::zeros({1}, X.options().dtype(torch::kFloat64));
+  if (n == 0 || k == 0) return {sums, counts, inertia};
+  auto sorted = labels.to(torch::kInt64).sort();
+  auto perm = std::get<1>(sorted).contiguous();
+  auto sl = std::get<0>(sorted).contiguous();
+  auto bounds = torch::arange(k + 1, labels.options().dtype(torch::kInt64));
+  auto seg_off = torch::searchsorted(sl, bounds).contiguous();
+  const bool aligned = ((uintptr_t)X.data_ptr() | (uintptr_t)C.data_ptr()) % 16 == 0;
+  if (vec && d % 4 == 0 && aligned)
+    hipLaunchKernelGGL(segment_sum_inertia_kernel<true>, dim3((unsigned)(k * LA_SPLIT)),
+                       dim3(256), 0, cur_stream(), X.data_ptr<float>(),
+                       perm.data_ptr<int64_t>(), seg_off.data_ptr<int64_t>(),
+                       C.data_ptr<float>(), d, sums.data_ptr<float>(),
+                       counts.data_ptr<float>(), inertia.data_ptr<double>());
+  else
+    hipLaunchKernelGGL(segment_sum_inertia_kernel<false>, dim3((unsigned)(k * LA_SPLIT)),
+                       dim3(256), 0, cur_stream(), X.data_ptr<float>(),
+                       perm.data_ptr<int64_t>(), seg_off.data_ptr<int64_t>(),
+                       C.data_ptr<float>(), d, sums.data_ptr<float>(),
+                       counts.data_ptr<float>(), inertia.data_ptr<double>());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return {sums, counts, inertia};
+}
+
 torch::Tensor gram_f32(torch::Tensor A) {
   TORCH_CHECK(A.is_cuda() && A.dtype() == torch::kFloat32 && A.is_contiguous());
   const int64_t n = A.size(0);
@@ -2578,30 +2769,41 @@ std::vector<torch::Tensor> kmeans_argmin_nk(torch::Tensor dots, torch::Tensor x_
   return {labels, min_d, inertia};
 }
 
-std::vector<torch::Tensor> kmeans_split_bf16(torch::Tensor A, torch::Tensor mu) {
+template <bool LO>
+static std::vector<torch::Tensor> kmeans_split_impl(torch::Tensor A, torch::Tensor mu) {
   TORCH_CHECK(A.is_cuda() && A.dtype() == torch::kFloat32 && A.is_contiguous());
   TORCH_CHECK(mu.is_cuda() && mu.dtype() == torch::kFloat32 && mu.is_contiguous());
   TORCH_CHECK(A.dim() == 2 && mu.numel() == A.size(1), "mu must have one entry per column");
   const int64_t m = A.size(0);
   const int d = (int)A.size(1);
   const int dp = (d + 31) / 32 * 32;
-  auto S = torch::empty({m, (int64_t)2 * dp}, A.options().dtype(torch::kBFloat16));
+  auto S = torch::empty({m, (int64_t)(LO ? 2 : 1) * dp}, A.options().dtype(torch::kBFloat16));
   auto a_sq = torch::empty({m}, A.options());
   if (m > 0) {
     const unsigned grid = (unsigned)std::min<int64_t>(1 << 20, (m + 3) / 4);
     auto* Sp = reinterpret_cast<uint16_t*>(S.data_ptr());
     const bool aligned = ((uintptr_t)A.data_ptr() | (uintptr_t)mu.data_ptr()) % 16 == 0;
     if (d % 4 == 0 && aligned)
-      hipLaunchKernelGGL(kmeans_split_bf16_kernel<true>, dim3(grid), dim3(256), 0,
+      hipLaunchKernelGGL((kmeans_split_bf16_kernel<true, LO>), dim3(grid), dim3(256), 0,
                          cur_stream(), A.data_ptr<float>(), mu.data_ptr<float>(), m, d,
                          dp, Sp, a_sq.data_ptr<float>());
     else
-      hipLaunchKernelGGL(kmeans_split_bf16_kernel<false>, dim3(grid), dim3(256), 0,
+      hipLaunchKernelGGL((kmeans_split_bf16_kernel<false, LO>), dim3(grid), dim3(256), 0,
                          cur_stream(), A.data_ptr<float>(), mu.data_ptr<float>(), m, d,
                          dp, Sp, a_sq.data_ptr<float>());
     C10_HIP_KERNEL_LAUNCH_CHECK();
   }
   return {S, a_sq};
+}
+
+std::vector<torch::Tensor> kmeans_split_bf16(torch::Tensor A, torch::Tensor mu) {
+  return kmeans_split_impl<true>(A, mu);
+}
+
+// (H [m, dp] bf16, a_sq [m]): the hi half and the a_sq of kmeans_split_bf16,
+// bit for bit, without the lo half.
+std::vector<torch::Tensor> kmeans_split_bf16_hi(torch::Tensor A, torch::Tensor mu) {
+  return kmeans_split_impl<false>(A, mu);
 }
 
 std::vector<torch::Tensor> kmeans_argmin_kn_screen(torch::Tensor dots, torch::Tensor a_sq,
@@ -2923,9 +3125,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("kmeans_argmin_kn", &kmeans_argmin_kn, "argmin epilogue over a [k,n] GEMM dot block");
   m.def("kmeans_argmin_nk", &kmeans_argmin_nk, "argmin epilogue over a row-major [m,k] GEMM dot block");
   m.def("kmeans_split_bf16", &kmeans_split_bf16, "centre + split f32 rows into bf16 hi|lo halves, with |x'|^2");
+  m.def("kmeans_split_bf16_hi", &kmeans_split_bf16_hi, "centre + round f32 rows to their bf16 hi plane, with |x'|^2");
   m.def("kmeans_argmin_kn_screen", &kmeans_argmin_kn_screen, "best/second argmin over a screened [k,n] dot block; flags near-ties");
   m.def("kmeans_refine", &kmeans_refine, "exact f64 decision for the flagged rows");
   m.def("label_accumulate", &label_accumulate, "per-center sum/count scatter");
+  m.def("label_accumulate_inertia", &label_accumulate_inertia, "sorted per-center sum/count + sum (x - c)^2 in the same pass",
+        py::arg("X"), py::arg("labels"), py::arg("C"), py::arg("vec") = LA_VEC_DEFAULT);
   m.def("gram_f32", &gram_f32, "A^T A via MFMA f32");
   m.def("softmax_residual_loss", &softmax_residual_loss, "fused softmax residual + loss");
   m.def("knn_select", &knn_select, "fused MFMA distance + in-LDS top-k");

@@ -8,14 +8,24 @@ decides them (`_refine_f32`) or, on request, in f64 by `kmeans_refine`
 (`_assign_split`). Otherwise the f32 library GEMM + `kmeans_argmin_kn` /
 `kmeans_argmin_nk` epilogues (`_assign_gemm`), or `kmeans_assign` — LDS-tiled
 ‖x‖²+‖c‖²−2x·c on mfma_f32_32x32x2f32 with a fused per-row argmin.
-`label_accumulate` is the vectorized per-center sum/count scatter. Together
-these are the KMeansMG Lloyd-step kernel family of the reference (SURVEY.md
-§2.3b, clustering.py:381-415).
+`label_accumulate` is the vectorized per-center sum/count scatter.
+
+Across the calls of one fit X does not change, so `kmeans_assign_reduce`
+keeps the centred bf16 hi plane of X and |x'|² (`_prepared`, one entry,
+SRML_KMEANS_CACHE=0 disables it) and screens with the hi·hi term alone
+(`_assign_prepared`): one K=dp GEMM instead of three terms and no split pass
+over X. A chunk with too many near-ties adds the other two terms onto the
+same dot block. That path reports the inertia `label_accumulate_inertia`
+sums beside the accumulation, as (x − c)² directly.
+
+Together these are the KMeansMG Lloyd-step kernel family of the reference
+(clustering.py:381-415).
 """
 
 from __future__ import annotations
 
 import os
+import weakref
 from typing import Optional, Tuple
 
 import torch
@@ -36,11 +46,36 @@ def kmeans_assign_reduce(
     profiles/README.md) + `label_accumulate`. SRML_KMEANS_VARIANT=f32 keeps
     the hipBLASLt f32 GEMM (141 TF) + `kmeans_argmin_kn` epilogue, =fused the
     all-in-one MFMA `kmeans_assign` kernel (84 TF), =split forces the screen
-    below D_MIN columns, =split_f64 also decides its near-ties in f64."""
+    below D_MIN columns, =split_f64 also decides its near-ties in f64.
+
+    Where the dispatch takes the screen and X is a contiguous device tensor,
+    the hi plane of X is prepared once and reused while the same X comes back
+    (`_prepared`; 9.8 against 27.4 ms per step, profiles/README.md). The
+    cache recognises X by identity, storage address, shape and torch's
+    version counter: a write to X that bypasses that counter (through
+    `.data`, a raw pointer, another library) is not seen.
+    SRML_KMEANS_CACHE=0 turns the cache off."""
     if use_hip(X) and X.dtype == torch.float32:
         ext = hip_ops()
+        if x_sq is None:
+            x_sq = _xsq(X)
+        if _cache_applies(X, C):
+            prep = _prepared(ext, X, C)
+            if prep is not None:
+                variant = os.environ.get("SRML_KMEANS_VARIANT")
+                labels, inertia = _assign_prepared(
+                    ext, X, C, x_sq, prep, exact=variant == "split_f64"
+                )
+                if inertia is None:
+                    sums, counts, inertia = ext.label_accumulate_inertia(
+                        X, labels, C.contiguous()
+                    )
+                else:  # ended in `_fallback_f32`
+                    sums, counts = ext.label_accumulate(X, labels, C.shape[0])
+                return (labels, sums.to(torch.float64), counts.to(torch.float64),
+                        float(inertia.item()))
         X = X.contiguous()
-        labels, inertia = _assign(ext, X, C, _xsq(X) if x_sq is None else x_sq)
+        labels, inertia = _assign(ext, X, C, x_sq)
         sums, counts = ext.label_accumulate(X, labels, C.shape[0])
         return labels, sums.to(torch.float64), counts.to(torch.float64), float(inertia.item())
     return torch_ref.kmeans_assign_reduce(X, C, x_sq)
@@ -244,6 +279,153 @@ def _assign_split(
         labels[s:e] = lb
         inertia += it
     return labels, inertia
+
+
+# One-term screen on the prepared hi plane (see `_assign_prepared`). With
+# u = 2^-9, hi·hi differs from the three-term product by at most
+# (2u + u²)·Σ|x'ᵢc'ᵢ| <= 2^-8 (1 + 2^-10) |x'||c'|, and SPLIT_EPS covers the
+# three-term product's own error with room for that 2^-18.
+EPS_HI = 2.0 ** -8 + SPLIT_EPS
+# Share of a chunk the hi screen may flag before the chunk falls up to the
+# three-term screen. Measured at 1M x 3000, k=1000 (tools/time_assign_split.py
+# --prepared; table in profiles/README.md): a fall-up costs 15.4 ms (split of
+# X 4.9, K=2·dp addmm 9.8, second screen 0.7), `_refine_f32` 51 to 71 ns per
+# flagged row, so the two meet near 28 % flagged; the cut-off sits below that.
+F_HI = 0.20
+
+
+class _Prepared:
+    """What a fit reuses of X: the centring point, the bf16 hi plane of X - mu
+    ([n, dp], zero pad columns) and |x - mu|², plus the key they belong to."""
+
+    __slots__ = ("ref", "key", "mu", "H", "a_sq", "finalizer")
+
+
+_PREP: Optional[_Prepared] = None
+
+
+def _key(X: torch.Tensor) -> tuple:
+    return (X._version, X.data_ptr(), tuple(X.shape))
+
+
+def _drop_prepared(token: Optional[_Prepared] = None) -> None:
+    """Empties the cache; with `token`, only if it still holds that entry."""
+    global _PREP
+    if token is None or _PREP is token:
+        if _PREP is not None:
+            _PREP.finalizer.detach()
+        _PREP = None
+
+
+def _cache_applies(X: torch.Tensor, C: torch.Tensor) -> bool:
+    """The gates of `_assign` that lead to `_assign_split`, for a contiguous
+    device X, unless SRML_KMEANS_CACHE=0."""
+    if os.environ.get("SRML_KMEANS_CACHE") == "0":
+        return False
+    if not (X.is_cuda and X.is_contiguous() and X.dim() == 2):
+        return False
+    n, k = X.shape[0], C.shape[0]
+    variant = os.environ.get("SRML_KMEANS_VARIANT")
+    if variant in ("f32", "fused") or k * 4 > 64 * 1024 or n == 0 or k < 384:
+        return False
+    return _use_split(variant, X.shape[1])
+
+
+def _prepared(ext, X: torch.Tensor, C: torch.Tensor) -> Optional[_Prepared]:
+    """The cache entry of X, built against the column mean of this C if X is
+    new (so the first call centres as `_assign_split` does). None, and today's
+    path, if the entry would take more than a quarter of the free device
+    memory. Dropped when X is collected, when another X or a modified X comes
+    in, and when a call ends in `_fallback_f32` (the next one re-centres)."""
+    global _PREP
+    p = _PREP
+    if p is not None and p.ref() is X and p.key == _key(X):
+        return p
+    _drop_prepared()
+    n, d = X.shape
+    dp = (d + 31) // 32 * 32
+    free, _total = torch.cuda.mem_get_info(X.device)
+    if n * dp * 2 + n * 4 > free // 4:
+        return None
+    p = _Prepared()
+    p.mu = C.contiguous().mean(dim=0)
+    p.H, p.a_sq = ext.kmeans_split_bf16_hi(X, p.mu)
+    p.ref = weakref.ref(X)
+    p.key = _key(X)
+    p.finalizer = weakref.finalize(X, _drop_prepared, p)
+    _PREP = p
+    return p
+
+
+def _assign_prepared(
+    ext, X: torch.Tensor, C: torch.Tensor, x_sq: torch.Tensor, prep: _Prepared,
+    max_dots_bytes: int = 8 << 30, exact: bool = False,
+) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """Two-stage screened assignment on the prepared hi plane: (labels, None),
+    the inertia being left to `label_accumulate_inertia`.
+
+    C is split against the cached mu (any fixed centring point keeps the
+    guarantee; mu is where C was when the entry was built). Per row chunk the
+    hi·hi dots, each within EPS_HI·|x'||c'| of exact, are screened with margin
+    4·EPS_HI·|x'|·max|c'|. At most F_HI of the chunk flagged: those rows are
+    decided as `_assign_split` decides its near-ties. More: the chunk falls
+    up — it is split in full against the same mu, `addmm` adds hi·lo + lo·hi
+    onto the same dot block, and it goes on exactly as `_assign_split` does
+    from its screen, F_MAX and `_fallback_f32` included; then the cache is
+    dropped and the result is (labels, inertia) of the f32 path."""
+    n, k = X.shape[0], C.shape[0]
+    Cc = C.contiguous()
+    mu, H = prep.mu, prep.H
+    SC, c_sq = ext.kmeans_split_bf16(Cc, mu)
+    dp = SC.shape[1] // 2
+    Ch = SC[:, :dp].contiguous()
+    ClCh = None
+    c_max = c_sq.max().sqrt()
+    margin_hi = ((4.0 * EPS_HI) * c_max).reshape(1)
+
+    rchunk = max(256, int(max_dots_bytes // (k * 4)))
+    single = rchunk >= n
+    labels = None if single else torch.empty(n, dtype=torch.int32, device=X.device)
+    dots = torch.empty((k, min(n, rchunk)), dtype=torch.float32, device=X.device)
+    for s in range(0, n, rchunk):
+        e = min(n, s + rchunk)
+        Xc = X[s:e]
+        a_sq = prep.a_sq[s:e]
+        if e - s != dots.shape[1]:
+            dots = torch.empty((k, e - s), dtype=torch.float32, device=X.device)
+        torch.mm(Ch, H[s:e].T, out_dtype=torch.float32, out=dots)
+        margin = margin_hi
+        lb, md, it, flagged, n_flagged = ext.kmeans_argmin_kn_screen(
+            dots, a_sq, c_sq, margin
+        )
+        nf = int(n_flagged.item())
+        if nf > F_HI * (e - s):
+            if ClCh is None:
+                ClCh = torch.cat([SC[:, dp:], SC[:, :dp]], dim=1)
+            SX, _a = ext.kmeans_split_bf16(Xc, mu)
+            # [Cl|Ch] @ [Xh|Xl]ᵀ = Cl·Xh + Ch·Xl, onto the hi·hi already there
+            torch.addmm(dots, ClCh, SX.T, out_dtype=torch.float32, out=dots)
+            del SX
+            margin = ((4.0 * SPLIT_EPS) * c_max).reshape(1)
+            lb, md, it, flagged, n_flagged = ext.kmeans_argmin_kn_screen(
+                dots, a_sq, c_sq, margin
+            )
+            nf = int(n_flagged.item())
+            if nf > F_MAX * (e - s):
+                _drop_prepared()
+                return _fallback_f32(ext, X, C, x_sq, n, k)
+        if nf and exact:
+            ext.kmeans_refine(
+                Xc, Cc, dots, c_sq, a_sq, margin, flagged, n_flagged, lb, md, it
+            )
+        elif nf:
+            rows = flagged[:nf].long()
+            lf, _itf = _refine_f32(ext, Xc, Cc, x_sq[s:e], rows)
+            lb[rows] = lf
+        if single:
+            return lb, None
+        labels[s:e] = lb
+    return labels, None
 
 
 def _xsq(X: torch.Tensor) -> torch.Tensor:

@@ -12,6 +12,11 @@ steps. Then the two sweeps behind ops/kmeans.py's D_MIN and F_MAX:
     (every row nearest a duplicated pair is flagged with two candidates).
     Blending all centres towards one row does not raise it: after centring
     that only scales c', and the margin scales with it (one line shows this).
+
+--prepared times the prepared-X step instead (`_assign_prepared`): the whole
+`kmeans_assign_reduce` with SRML_KMEANS_CACHE on and off over the first Lloyd
+steps (flagged share per step), then each part of the hi path and of a
+fall-up on the centres after those steps: the costs behind F_HI.
 """
 import argparse
 import sys
@@ -25,6 +30,7 @@ from spark_rapids_ml_amd.ops.dispatch import hip_ops
 ap = argparse.ArgumentParser()
 ap.add_argument("--quick", action="store_true", help="3 repeats, short sweeps")
 ap.add_argument("--rows", type=int, default=1_000_000)
+ap.add_argument("--prepared", action="store_true", help="time the prepared-X step only")
 args = ap.parse_args()
 
 real = hip_ops()
@@ -92,6 +98,84 @@ x_sq = (X * X).sum(dim=1)
 g0 = torch.Generator(device=dev)
 g0.manual_seed(42)
 C0 = torch.randn(k, d, generator=g0, device=dev)
+
+
+
+def med(fn, reps=REPS):
+    fn()
+    torch.cuda.synchronize()
+    ts = sorted(timed(fn) for _ in range(reps))
+    return ts[len(ts) // 2], ts[-1] - ts[0]
+
+
+def prepared_report():
+    import os
+
+    km.hip_ops = lambda: ext
+
+    def lloyd(C, steps, tag):
+        for i in range(steps):
+            flag_counts.clear()
+            t = timed(lambda: km.kmeans_assign_reduce(X, C, x_sq))
+            fl = [int(c.item()) for c in flag_counts]
+            labels, sums, counts, inertia = km.kmeans_assign_reduce(X, C, x_sq)
+            print(f"  {tag} step {i}: {t:.2f} ms  flagged per screen {fl}  "
+                  f"inertia {inertia!r}", flush=True)
+            nz = counts > 0
+            Cn = C.clone()
+            Cn[nz] = (sums[nz] / counts[nz, None]).float()
+            C = Cn
+        return C
+
+    os.environ["SRML_KMEANS_CACHE"] = "0"
+    lloyd(C0, 6, "cache off")
+    del os.environ["SRML_KMEANS_CACHE"]
+    C = lloyd(C0, 6, "cache on ")
+
+    for tag, env in (("cache off", "0"), ("cache on ", "1")):
+        os.environ["SRML_KMEANS_CACHE"] = env
+        t, sp = med(lambda: km.kmeans_assign_reduce(X, C, x_sq))
+        print(f"step on converged C, {tag}: {t:.2f} ms ({sp:.2f})", flush=True)
+    del os.environ["SRML_KMEANS_CACHE"]
+
+    prep = km._prepared(real, X, C)
+    SC, c_sq = real.kmeans_split_bf16(C, prep.mu)
+    dp = SC.shape[1] // 2
+    Ch = SC[:, :dp].contiguous()
+    ClCh = torch.cat([SC[:, dp:], SC[:, :dp]], dim=1)
+    dots = torch.empty((k, n), dtype=torch.float32, device=dev)
+    margin = ((4.0 * km.EPS_HI) * c_sq.max().sqrt()).reshape(1)
+    gb = dots.numel() * 4 / 1e9
+
+    def line(tag, r, extra=""):
+        print(f"  {tag:34s} {r[0]:7.2f} ms ({r[1]:.2f}) {extra}", flush=True)
+
+    line("hi split of X (once per fit)", med(lambda: real.kmeans_split_bf16_hi(X, prep.mu)))
+    r = med(lambda: torch.mm(Ch, prep.H.T, out_dtype=torch.float32, out=dots))
+    line("K=dp GEMM", r, f"{2.0 * n * k * dp / r[0] / 1e9:.0f} TF")
+    r = med(lambda: real.kmeans_argmin_kn_screen(dots, prep.a_sq, c_sq, margin))
+    line("kmeans_argmin_kn_screen", r, f"{gb / r[0]:.2f} TB/s")
+    r = med(lambda: real.kmeans_argmin_kn(dots, prep.a_sq, c_sq))
+    line("kmeans_argmin_kn, same block", r, f"{gb / r[0]:.2f} TB/s")
+    labels = real.kmeans_argmin_kn_screen(dots, prep.a_sq, c_sq, margin)[0]
+    line("label_accumulate", med(lambda: real.label_accumulate(X, labels, k)))
+    line("label_accumulate_inertia vec", med(lambda: real.label_accumulate_inertia(X, labels, C, True)))
+    line("label_accumulate_inertia scalar", med(lambda: real.label_accumulate_inertia(X, labels, C, False)))
+    SX = real.kmeans_split_bf16(X, prep.mu)[0]
+    line("fall-up: kmeans_split_bf16 of X", med(lambda: real.kmeans_split_bf16(X, prep.mu)))
+    line("fall-up: addmm K=2dp", med(
+        lambda: torch.addmm(dots, ClCh, SX.T, out_dtype=torch.float32, out=dots)))
+    del SX
+    for share in (0.01, 0.05, 0.10, 0.25):
+        rows = torch.randperm(n, device=dev)[: int(share * n)].sort().values
+        r = med(lambda: km._refine_f32(real, X, C, x_sq, rows), reps=3)
+        line(f"_refine_f32 on {100 * share:.0f} % of the rows", r,
+             f"{r[0] * 1e6 / rows.numel():.1f} ns/row")
+
+
+if args.prepared:
+    prepared_report()
+    sys.exit(0)
 
 # the screen must never fall back while it is being timed
 f_max = km.F_MAX
