@@ -23,6 +23,7 @@
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdint>
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
@@ -1954,8 +1955,13 @@ __device__ inline float wave_max_f32(float v) {
   return v;
 }
 
+// KEYS = true is the sibling entry point knn_merge_topk_keys: G already holds
+// the monotone distance keys of a pairwise_dist block (q_sq / i_sq are unused
+// and may be null), everything else — slots, tau, the uniform trip count — is
+// the same body.
+template <bool KEYS>
 __global__ __launch_bounds__(256) void knn_merge_topk_kernel(
-    const float* __restrict__ G,     // [nq, c] dot products Q @ I_chunk^T
+    const float* __restrict__ G,     // [nq, c] dot products Q @ I_chunk^T (or keys)
     const float* __restrict__ q_sq,  // [nq]
     const float* __restrict__ i_sq,  // [c]
     int64_t nq, int64_t c, int64_t base,
@@ -1971,7 +1977,7 @@ __global__ __launch_bounds__(256) void knn_merge_topk_kernel(
   float tau = wave_max_f32(cur_d);
 
   const float* g = G + row * c;
-  const float qs = q_sq[row];
+  const float qs = KEYS ? 0.0f : q_sq[row];
 
   // float4 loads are legal only when every row base is 16B-aligned, i.e.
   // c % 4 == 0 (g = G + row*c); otherwise scalar loads
@@ -1986,19 +1992,23 @@ __global__ __launch_bounds__(256) void knn_merge_topk_kernel(
     float dot4[4], isq4[4];
     if (vec4 && j0 + 3 < c) {
       const float4 gd = *reinterpret_cast<const float4*>(g + j0);
-      const float4 gi = *reinterpret_cast<const float4*>(i_sq + j0);
       dot4[0] = gd.x; dot4[1] = gd.y; dot4[2] = gd.z; dot4[3] = gd.w;
-      isq4[0] = gi.x; isq4[1] = gi.y; isq4[2] = gi.z; isq4[3] = gi.w;
+      if constexpr (!KEYS) {
+        const float4 gi = *reinterpret_cast<const float4*>(i_sq + j0);
+        isq4[0] = gi.x; isq4[1] = gi.y; isq4[2] = gi.z; isq4[3] = gi.w;
+      }
     } else {
       for (int e = 0; e < 4; ++e) {
         const bool ok = j0 + e < c;
         dot4[e] = ok ? g[j0 + e] : 0.0f;
-        isq4[e] = ok ? i_sq[j0 + e] : 3.0e38f;  // pushes d2 above any tau
+        if constexpr (!KEYS)
+          isq4[e] = ok ? i_sq[j0 + e] : 3.0e38f;  // pushes d2 above any tau
       }
     }
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      const float d2 = qs + isq4[e] - 2.0f * dot4[e];
+      // KEYS: a padded column carries key 0 and is masked by j0 + e < c below
+      const float d2 = KEYS ? dot4[e] : qs + isq4[e] - 2.0f * dot4[e];
       unsigned long long m = __ballot(d2 < tau && j0 + e < c);
       while (m) {
         const int src = __ffsll((unsigned long long)m) - 1;
@@ -2017,6 +2027,154 @@ __global__ __launch_bounds__(256) void knn_merge_topk_kernel(
 
   best_d[row * 64 + lane] = cur_d;
   best_i[row * 64 + lane] = cur_i;
+}
+
+// ---------------------------------------------------------------------------
+// pairwise_dist: one [nq, c] block of distance KEYS of queries Q against an
+// item chunk, for the metrics that are per-coordinate reductions with no
+// GEMM / MFMA form (L1, Linf, Lp, canberra, hamming). It plays the role the
+// library GEMM's dot block plays on the euclidean path: knn_merge_topk_keys
+// consumes the block once.
+//
+// 256 threads own one 128x128 output tile; each thread an 8x8 accumulator
+// micro-tile split 4+4 in both directions (rows ty*4.. and 64+ty*4.., columns
+// tx*4.. and 64+tx*4..) so that each operand fetch of one coordinate is a
+// pair of ds_read_b128 whose 16 distinct lane addresses are 16 B apart: 256
+// contiguous bytes, one per bank slot (the Q side reads 4 addresses per wave,
+// broadcast). d is walked in PD_BK-coordinate chunks staged k-major ([t][row])
+// in LDS; the next chunk is fetched to registers while the current one is
+// reduced and written to the other LDS buffer, one barrier per chunk.
+// Rows past nq / c and coordinates past d are staged as 0 on BOTH sides:
+// |0-0| = 0 is the identity of sum and max, 0 == 0 is no hamming mismatch,
+// and canberra's 0/0 term is defined as 0.
+// The kernel emits the monotone key (sum, max, sum |.|^p, mismatch count);
+// the host applies the p-th root / the division by d to the k survivors.
+// ---------------------------------------------------------------------------
+
+constexpr int PD_BM = 128;
+constexpr int PD_BK = 16;
+constexpr int PD_LD = PD_BM + 4;  // row stride: keeps float4 alignment, and the
+                                  // transposing stores of one wave 2-way at
+                                  // most (free for ds_write_b32)
+constexpr int PD_ST = PD_BM * PD_BK / 256;  // staged elements per thread (8)
+
+enum { PD_L1 = 0, PD_LINF = 1, PD_LP = 2, PD_CANBERRA = 3, PD_HAMMING = 4 };
+
+template <int OP>
+__device__ inline float pd_accum(float acc, float q, float x, float p) {
+  if constexpr (OP == PD_L1) {
+    return acc + fabsf(q - x);
+  } else if constexpr (OP == PD_LINF) {
+    return fmaxf(acc, fabsf(q - x));
+  } else if constexpr (OP == PD_LP) {
+    // |q-x|^p = 2^(p*log2|q-x|) on the transcendental unit: p is a kernel
+    // argument (wave-uniform), no per-lane powf case analysis. log2(0) = -inf
+    // and 2^-inf = 0, so equal coordinates (and padding) contribute 0.
+    return acc + __builtin_amdgcn_exp2f(p * __builtin_amdgcn_logf(fabsf(q - x)));
+  } else if constexpr (OP == PD_CANBERRA) {
+    const float den = fabsf(q) + fabsf(x);
+    const float t = fabsf(q - x) * __builtin_amdgcn_rcpf(den);
+    return acc + (den > 0.0f ? t : 0.0f);  // 0/0 = 0
+  } else {
+    return acc + (q != x ? 1.0f : 0.0f);
+  }
+}
+
+template <int OP>
+__global__ __launch_bounds__(256) void pairwise_dist_kernel(
+    const float* __restrict__ Q,  // [nq, d]
+    const float* __restrict__ I,  // [c, d] item chunk
+    int64_t nq, int64_t c, int d, float p, int64_t n_it,
+    float* __restrict__ out) {    // [nq, c]
+  __shared__ __attribute__((aligned(16))) float Qs[2][PD_BK][PD_LD];
+  __shared__ __attribute__((aligned(16))) float Is[2][PD_BK][PD_LD];
+
+  const int tid = threadIdx.x;
+  const int tx = tid & 15;
+  const int ty = tid >> 4;
+  const int64_t q0 = ((int64_t)blockIdx.x / n_it) * PD_BM;
+  const int64_t i0 = ((int64_t)blockIdx.x % n_it) * PD_BM;
+
+  // staging map: element e of this thread is (row, t) = (lin / BK, lin % BK)
+  // with lin = tid + 256 e, i.e. row = (tid >> 4) + 16 e, t = tid & 15:
+  // 16 consecutive lanes read 64 contiguous bytes of one row
+  const int st = tid & (PD_BK - 1);
+  const int sr = tid >> 4;
+  float rq[PD_ST], ri[PD_ST];
+
+  auto fetch = [&](int k0) {
+    const int t = k0 + st;
+    const bool tok = t < d;
+#pragma unroll
+    for (int e = 0; e < PD_ST; ++e) {
+      const int64_t qr = q0 + sr + 16 * e;
+      const int64_t ir = i0 + sr + 16 * e;
+      rq[e] = (tok && qr < nq) ? Q[qr * d + t] : 0.0f;
+      ri[e] = (tok && ir < c) ? I[ir * d + t] : 0.0f;
+    }
+  };
+  auto stage = [&](int buf) {
+#pragma unroll
+    for (int e = 0; e < PD_ST; ++e) {
+      Qs[buf][st][sr + 16 * e] = rq[e];
+      Is[buf][st][sr + 16 * e] = ri[e];
+    }
+  };
+
+  float acc[8][8];
+#pragma unroll
+  for (int a = 0; a < 8; ++a)
+#pragma unroll
+    for (int b = 0; b < 8; ++b) acc[a][b] = 0.0f;
+
+  const int n_chunks = (d + PD_BK - 1) / PD_BK;
+  fetch(0);
+  stage(0);
+  __syncthreads();
+  for (int ch = 0; ch < n_chunks; ++ch) {
+    const int buf = ch & 1;
+    const bool more = ch + 1 < n_chunks;  // block-uniform
+    if (more) fetch((ch + 1) * PD_BK);
+    // unrolled by 2 only: a full unroll lets the scheduler hoist every LDS
+    // read of the chunk above the arithmetic (256+ live registers, spills)
+#pragma unroll 2
+    for (int t = 0; t < PD_BK; ++t) {
+      const float4 qa = *reinterpret_cast<const float4*>(&Qs[buf][t][ty * 4]);
+      const float4 qb = *reinterpret_cast<const float4*>(&Qs[buf][t][64 + ty * 4]);
+      const float4 xa = *reinterpret_cast<const float4*>(&Is[buf][t][tx * 4]);
+      const float4 xb = *reinterpret_cast<const float4*>(&Is[buf][t][64 + tx * 4]);
+      const float qv[8] = {qa.x, qa.y, qa.z, qa.w, qb.x, qb.y, qb.z, qb.w};
+      const float xv[8] = {xa.x, xa.y, xa.z, xa.w, xb.x, xb.y, xb.z, xb.w};
+#pragma unroll
+      for (int a = 0; a < 8; ++a)
+#pragma unroll
+        for (int b = 0; b < 8; ++b) acc[a][b] = pd_accum<OP>(acc[a][b], qv[a], xv[b], p);
+    }
+    // the other buffer was last read in iteration ch-1, which every thread
+    // left through the barrier below
+    if (more) stage(buf ^ 1);
+    __syncthreads();
+  }
+
+  const bool vec4 = (c & 3) == 0;  // every row base of out is then 16B-aligned
+#pragma unroll
+  for (int a = 0; a < 8; ++a) {
+    const int64_t row = q0 + (a < 4 ? ty * 4 + a : 64 + ty * 4 + (a - 4));
+    if (row >= nq) continue;
+    float* o = out + row * c;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int64_t col = i0 + h * 64 + tx * 4;
+      if (vec4 && col + 3 < c) {
+        *reinterpret_cast<float4*>(o + col) =
+            make_float4(acc[a][4 * h], acc[a][4 * h + 1], acc[a][4 * h + 2], acc[a][4 * h + 3]);
+      } else {
+#pragma unroll
+        for (int b = 0; b < 4; ++b)
+          if (col + b < c) o[col + b] = acc[a][4 * h + b];
+      }
+    }
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -2929,10 +3087,72 @@ void knn_merge_topk(torch::Tensor G, torch::Tensor q_sq, torch::Tensor i_sq,
   const int64_t nq = G.size(0);
   const int64_t c = G.size(1);
   TORCH_CHECK(i_sq.size(0) == c && q_sq.size(0) == nq && best_d.size(0) == nq);
-  hipLaunchKernelGGL(knn_merge_topk_kernel, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0,
+  hipLaunchKernelGGL(knn_merge_topk_kernel<false>, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0,
                      cur_stream(), G.data_ptr<float>(), q_sq.data_ptr<float>(),
                      i_sq.data_ptr<float>(), nq, c, base, best_d.data_ptr<float>(),
                      best_i.data_ptr<int64_t>());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+}
+
+void knn_merge_topk_keys(torch::Tensor G, int64_t base, torch::Tensor best_d,
+                         torch::Tensor best_i) {
+  TORCH_CHECK(G.is_cuda() && G.dtype() == torch::kFloat32 && G.is_contiguous() && G.dim() == 2);
+  TORCH_CHECK(best_d.is_cuda() && best_d.dtype() == torch::kFloat32 && best_d.dim() == 2);
+  TORCH_CHECK(best_i.is_cuda() && best_i.dtype() == torch::kInt64 && best_i.dim() == 2);
+  TORCH_CHECK(best_d.size(1) == 64 && best_i.size(1) == 64,
+              "slot buffers must be [nq, 64]");
+  TORCH_CHECK(best_d.is_contiguous() && best_i.is_contiguous());
+  const int64_t nq = G.size(0);
+  const int64_t c = G.size(1);
+  TORCH_CHECK(best_d.size(0) == nq && best_i.size(0) == nq);
+  if (nq == 0 || c == 0) return;
+  hipLaunchKernelGGL(knn_merge_topk_kernel<true>, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0,
+                     cur_stream(), G.data_ptr<float>(), (const float*)nullptr,
+                     (const float*)nullptr, nq, c, base, best_d.data_ptr<float>(),
+                     best_i.data_ptr<int64_t>());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+}
+
+template <int OP>
+static void pairwise_dist_launch(unsigned grid, const float* Q, const float* I, int64_t nq,
+                                 int64_t c, int d, float p, int64_t n_it, float* out) {
+  hipLaunchKernelGGL(pairwise_dist_kernel<OP>, dim3(grid), dim3(256), 0, cur_stream(), Q, I,
+                     nq, c, d, p, n_it, out);
+}
+
+// op: 0 L1 (sum |q-x|), 1 Linf (max), 2 Lp (sum |q-x|^p, no root), 3 canberra,
+// 4 hamming (mismatch count, not divided by d)
+void pairwise_dist(torch::Tensor Q, torch::Tensor I, int64_t op, double p, torch::Tensor out) {
+  TORCH_CHECK(Q.is_cuda() && Q.dtype() == torch::kFloat32 && Q.is_contiguous() && Q.dim() == 2);
+  TORCH_CHECK(I.is_cuda() && I.dtype() == torch::kFloat32 && I.is_contiguous() && I.dim() == 2);
+  TORCH_CHECK(out.is_cuda() && out.dtype() == torch::kFloat32 && out.is_contiguous() &&
+              out.dim() == 2);
+  const int64_t nq = Q.size(0);
+  const int64_t c = I.size(0);
+  TORCH_CHECK(Q.size(1) == I.size(1), "Q and I must have the same number of columns");
+  TORCH_CHECK(Q.size(1) >= 1 && Q.size(1) < (int64_t(1) << 24),
+              "pairwise_dist supports 1 <= d < 2^24");
+  TORCH_CHECK(out.size(0) == nq && out.size(1) == c, "out must be [nq, c]");
+  TORCH_CHECK(op >= PD_L1 && op <= PD_HAMMING, "unknown pairwise_dist op");
+  TORCH_CHECK(op != PD_LP || (std::isfinite(p) && p > 0.0), "minkowski p must be finite and > 0");
+  if (nq == 0 || c == 0) return;
+  const int d = (int)Q.size(1);
+  const int64_t n_qt = (nq + PD_BM - 1) / PD_BM;
+  const int64_t n_it = (c + PD_BM - 1) / PD_BM;
+  TORCH_CHECK(n_qt * n_it < (int64_t(1) << 31), "pairwise_dist block is too large");
+  const unsigned grid = (unsigned)(n_qt * n_it);
+  const float* q = Q.data_ptr<float>();
+  const float* it = I.data_ptr<float>();
+  float* o = out.data_ptr<float>();
+  switch (op) {
+    case PD_L1: pairwise_dist_launch<PD_L1>(grid, q, it, nq, c, d, (float)p, n_it, o); break;
+    case PD_LINF: pairwise_dist_launch<PD_LINF>(grid, q, it, nq, c, d, (float)p, n_it, o); break;
+    case PD_LP: pairwise_dist_launch<PD_LP>(grid, q, it, nq, c, d, (float)p, n_it, o); break;
+    case PD_CANBERRA:
+      pairwise_dist_launch<PD_CANBERRA>(grid, q, it, nq, c, d, (float)p, n_it, o);
+      break;
+    default: pairwise_dist_launch<PD_HAMMING>(grid, q, it, nq, c, d, (float)p, n_it, o); break;
+  }
   C10_HIP_KERNEL_LAUNCH_CHECK();
 }
 
@@ -3142,6 +3362,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rf_partition", &rf_partition, "counting-sort rows by node -> (perm, seg_off)");
   m.def("rf_reroute", &rf_reroute, "one-pass row-to-child reassignment");
   m.def("knn_merge_topk", &knn_merge_topk, "running top-k merge over a GEMM dot block");
+  m.def("knn_merge_topk_keys", &knn_merge_topk_keys,
+        "running top-k merge over a block of distance keys");
+  m.def("pairwise_dist", &pairwise_dist,
+        "register-tiled all-pairs distance keys (L1, Linf, Lp, canberra, hamming)");
   m.def("gather_dists", &gather_dists, "gathered row-vs-candidates squared distances");
   m.def("ivf_scan_topk", &ivf_scan_topk, "fused IVF-Flat probed-list scan + running top-k");
   m.attr("_is_hip") = true;

@@ -27,7 +27,8 @@ from ..params import (
     Param,
     TypeConverters,
 )
-from ..ops.knn import knn_topk
+from ..ops.knn import knn_topk, knn_topk_metric, resolve_metric
+from ..ops import torch_ref
 from ..utils import as_numpy
 
 
@@ -96,6 +97,21 @@ def _fuzzy_simplicial_set(
     sym = set_op_mix_ratio * (W + Wt - prod) + (1 - set_op_mix_ratio) * prod
     sym = sym.tocoo()
     return sym.row.astype(np.int64), sym.col.astype(np.int64), sym.data.astype(np.float32)
+
+
+def _drop_self(d: torch.Tensor, i: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Drop each row's own index from its k+1 sorted neighbours. With
+    duplicate rows, or cosine's rounding, the self match need not be column
+    0: remove the entry whose index equals the row where present, otherwise
+    the last one. Order is kept."""
+    n, k1 = i.shape
+    is_self = i == torch.arange(n, device=i.device)[:, None]
+    drop = torch.where(
+        is_self.any(dim=1), is_self.to(torch.int64).argmax(dim=1),
+        torch.full((n,), k1 - 1, dtype=torch.int64, device=i.device),
+    )
+    keep = torch.arange(k1, device=i.device)[None, :] != drop[:, None]
+    return d[keep].reshape(n, k1 - 1).contiguous(), i[keep].reshape(n, k1 - 1).contiguous()
 
 
 def _smooth_knn_t(dists: torch.Tensor, local_connectivity: float = 1.0) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -325,9 +341,15 @@ class _UMAPParams(HasFeaturesCol, HasFeaturesCols, HasLabelCol, HasOutputCol):
     sample_fraction = Param(
         "umap", "sample_fraction", "fit subsample fraction (reference umap.py:923-945).", TypeConverters.toFloat
     )
-    metric = Param("umap", "metric", "distance metric (euclidean/l2).", TypeConverters.toString)
+    metric = Param(
+        "umap", "metric",
+        "distance metric of the kNN graph: l1/cityblock/taxicab/manhattan, "
+        "euclidean/l2, sqeuclidean, canberra, minkowski, chebyshev/linf, cosine, "
+        "correlation, hellinger, hamming (jaccard needs sparse input: unsupported).",
+        TypeConverters.toString,
+    )
     metric_kwds = Param(
-        "umap", "metric_kwds", "metric kwargs (accepted; euclidean needs none).",
+        "umap", "metric_kwds", "metric kwargs: {'p': ...} for minkowski (default 2).",
         DictTypeConverters._toDict,
     )
     build_algo = Param(
@@ -371,6 +393,11 @@ class _UMAPParams(HasFeaturesCol, HasFeaturesCols, HasLabelCol, HasOutputCol):
             outputCol="embedding",
         )
 
+    def _metric(self) -> Tuple[str, float]:
+        """(canonical metric, p) from `metric` and `metric_kwds`."""
+        kwds = self.getOrDefault("metric_kwds") or {}
+        return resolve_metric(self.getOrDefault("metric"), kwds.get("p", 2.0))
+
     @classmethod
     def _param_mapping(cls) -> Dict[str, Optional[str]]:
         return {p: p for p in [
@@ -383,10 +410,15 @@ class _UMAPParams(HasFeaturesCol, HasFeaturesCols, HasLabelCol, HasOutputCol):
 
     @classmethod
     def _param_value_mapping(cls):
-        # euclidean distances only (reference passes other metrics to cuML;
-        # unsupported values must error, not silently compute euclidean)
+        def _metric(v):
+            # jaccard is a documented name: it passes here and reaches the
+            # dense-input error at fit; an unknown name lists the accepted ones
+            if str(v).lower() != "jaccard":
+                resolve_metric(v)
+            return v
+
         return {
-            "metric": lambda v: v if v in ("euclidean", "l2") else None,
+            "metric": _metric,
             "build_algo": lambda v: v
             if v in ("auto", "brute_force_knn", "nn_descent")
             else None,
@@ -398,8 +430,8 @@ class _UMAPParams(HasFeaturesCol, HasFeaturesCols, HasLabelCol, HasOutputCol):
             "n_neighbors": 15,
             "n_components": 2,
             "verbose": False,
-            # cuML-signature knobs accepted for ctor parity (inert here:
-            # euclidean metric; graph build auto-selects brute/nn-descent)
+            # cuML-signature knobs (transform_queue_size and precomputed_knn
+            # are inert here; graph build auto-selects brute/nn-descent)
             "metric": "euclidean",
             "metric_kwds": None,
             "transform_queue_size": 4.0,
@@ -513,26 +545,50 @@ class UMAP(_UMAPParams, Estimator):
         dim = int(self.getOrDefault("n_components"))
         seed = int(self.getOrDefault("random_state"))
         Xt = to_device_tensor(X, device)
+        metric, p = self._metric()
         build_algo = str(self.getOrDefault("build_algo") or "auto").lower()
-        brute = build_algo == "brute_force_knn" or (build_algo == "auto" and n <= 50000)
-        if brute:
+        # nn-descent works in L2 (the reference states it supports only L2):
+        # cosine / correlation qualify on their transformed rows, the tile
+        # metrics and hellinger always build by brute force
+        l2_rows = metric in ("euclidean", "sqeuclidean", "cosine", "correlation")
+        if build_algo == "nn_descent" and not l2_rows:
+            raise ValueError(
+                f"build_algo='nn_descent' supports only L2-reducible metrics (euclidean, "
+                f"sqeuclidean, cosine, correlation); metric={metric!r} needs "
+                f"build_algo='brute_force_knn' or 'auto'"
+            )
+        brute = (
+            build_algo == "brute_force_knn"
+            or (build_algo == "auto" and n <= 50000)
+            or not l2_rows
+        )
+        if brute and metric == "euclidean":
             d, i = knn_topk(Xt, Xt, k + 1)
+        elif brute:
+            d, i = knn_topk_metric(Xt, Xt, k + 1, metric, p)
         else:
             # nn-descent graph (reference switches off brute force above 50k
             # rows, umap.py:359-366); reuse the CAGRA build
             from .knn import _nn_descent, _batched_dists
 
-            G = _nn_descent(Xt, max(k + 1, 32), 5)
+            unit = metric in ("cosine", "correlation")
+            Xn = torch_ref.metric_rows(Xt, metric) if unit else Xt
+            G = _nn_descent(Xn, max(k + 1, 32), 5)
             rows = torch.arange(n, device=Xt.device)
-            Gd = _batched_dists(Xt, rows, G)
+            Gd = _batched_dists(Xn, rows, G)
             vals, order = torch.sort(Gd, dim=1)
             i = torch.cat([rows[:, None], G.gather(1, order)[:, :k]], dim=1)
-            d = torch.cat(
-                [torch.zeros(n, 1, device=Xt.device), torch.sqrt(vals[:, :k])], dim=1
-            )
+            if unit:  # ||a-b||^2 = 2 (1 - <a,b>) on unit rows
+                vals = 0.5 * vals
+            elif metric == "euclidean":
+                vals = torch.sqrt(vals)
+            d = torch.cat([torch.zeros(n, 1, device=Xt.device), vals[:, :k]], dim=1)
         _t0 = _mark("knn_graph", _t0)
-        knn_d_t = d[:, 1:].contiguous()  # drop self column
-        knn_i_t = i[:, 1:].contiguous()
+        if metric == "euclidean" or not brute:
+            knn_d_t = d[:, 1:].contiguous()  # drop self column
+            knn_i_t = i[:, 1:].contiguous()
+        else:
+            knn_d_t, knn_i_t = _drop_self(d, i)
 
         rows_t, cols_t, vals_t = _fuzzy_simplicial_set_t(
             knn_d_t,
@@ -660,7 +716,11 @@ class UMAPModel(_UMAPParams, Model):
         emb = to_device_tensor(self.embedding, device)
         k = int(float(self.getOrDefault("n_neighbors")))
         k = min(k, raw.shape[0])
-        d, i = knn_topk(Xt, raw, k)
+        metric, p = self._metric()
+        if metric == "euclidean":
+            d, i = knn_topk(Xt, raw, k)
+        else:
+            d, i = knn_topk_metric(Xt, raw, k, metric, p)
         # device-resident smooth-knn + membership weights (the numpy hop
         # cost seconds at 1M transform rows)
         sigma, rho = _smooth_knn_t(d, float(self.getOrDefault("local_connectivity")))

@@ -5,11 +5,17 @@ blocks, fusing the ||q-i||^2 expansion (MFMA) with per-query top-k candidate
 pools held in LDS — the [nq, ni] distance matrix is never materialized
 (reference NearestNeighborsMG tiled distance + top-k).
 Falls back to the chunked torch path for k > 64 or CPU.
+
+`knn_topk_metric` serves the metrics other than euclidean (UMAP's `metric`):
+dot-product metrics on preprocessed rows through the same GEMM + selection
+path, per-coordinate metrics through the `pairwise_dist` tile kernel +
+`knn_merge_topk_keys`.
 """
 
 from __future__ import annotations
 
-from typing import Tuple
+import math
+from typing import Callable, Dict, Tuple
 
 import torch
 
@@ -49,15 +55,18 @@ def knn_topk(Q: torch.Tensor, I: torch.Tensor, k: int) -> Tuple[torch.Tensor, to
     return torch_ref.knn_topk(Q, I, k)
 
 
-def _knn_topk_gemm_select(
-    Q: torch.Tensor, I: torch.Tensor, k: int, chunk_elems: int = 1 << 29
+def _chunked_select(
+    nq: int,
+    ni: int,
+    k: int,
+    dev: torch.device,
+    chunk_elems: int,
+    merge_chunk: Callable[[torch.Tensor, int, int, torch.Tensor, torch.Tensor], None],
 ) -> Tuple[torch.Tensor, torch.Tensor]:
-    """Library GEMM + own running-top-k selection kernel (see knn_topk)."""
-    ext = hip_ops()
-    nq, ni = Q.shape[0], I.shape[0]
-    dev = Q.device
-    q_sq = (Q * Q).sum(dim=1).contiguous()
-    i_sq = (I * I).sum(dim=1).contiguous()
+    """Running 64-slot top-k over item chunks: `merge_chunk(Gv, s, e, best_d,
+    best_i)` fills the [nq, e-s] scratch block Gv for items s:e and merges it
+    into the slots. Returns the k smallest keys per row, ascending, and their
+    item indices."""
     # 64 candidate slots per query; lanes >= k carry a -inf sentinel so they
     # never own tau (the running worst kept distance) inside the kernel
     best_d = torch.full((nq, 64), float("inf"), dtype=torch.float32, device=dev)
@@ -75,14 +84,150 @@ def _knn_topk_gemm_select(
         Gv = G if e - s == G.shape[1] else torch.empty(
             (nq, e - s), dtype=torch.float32, device=dev
         )
-        torch.mm(Q, I[s:e].T, out=Gv)
-        ext.knn_merge_topk(Gv, q_sq, i_sq[s:e].contiguous(), s, best_d, best_i)
+        merge_chunk(Gv, s, e, best_d, best_i)
 
     if k < 64:
         best_d[:, k:] = float("inf")  # dead slots sort last
     d_sorted, order = torch.sort(best_d, dim=1)
     i_sorted = best_i.gather(1, order)
-    return (
-        torch.sqrt(torch.clamp(d_sorted[:, :k], min=0.0)),
-        i_sorted[:, :k].contiguous(),
+    return d_sorted[:, :k], i_sorted[:, :k].contiguous()
+
+
+def _gemm_select_keys(
+    Q: torch.Tensor,
+    I: torch.Tensor,
+    q_sq: torch.Tensor,
+    i_sq: torch.Tensor,
+    k: int,
+    chunk_elems: int,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """k smallest q_sq[r] + i_sq[j] - 2 <Q[r], I[j]> per row: library GEMM for
+    the dot block + the own `knn_merge_topk` selection kernel."""
+    ext = hip_ops()
+
+    def merge_chunk(Gv, s, e, best_d, best_i):
+        torch.mm(Q, I[s:e].T, out=Gv)
+        ext.knn_merge_topk(Gv, q_sq, i_sq[s:e].contiguous(), s, best_d, best_i)
+
+    return _chunked_select(Q.shape[0], I.shape[0], k, Q.device, chunk_elems, merge_chunk)
+
+
+def _knn_topk_gemm_select(
+    Q: torch.Tensor, I: torch.Tensor, k: int, chunk_elems: int = 1 << 29
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Library GEMM + own running-top-k selection kernel (see knn_topk)."""
+    q_sq = (Q * Q).sum(dim=1).contiguous()
+    i_sq = (I * I).sum(dim=1).contiguous()
+    d2, idx = _gemm_select_keys(Q, I, q_sq, i_sq, k, chunk_elems)
+    return torch.sqrt(torch.clamp(d2, min=0.0)), idx
+
+
+# ---------------------------------------------------------------------------
+# metrics other than euclidean (UMAP's `metric`; scipy cdist definitions)
+# ---------------------------------------------------------------------------
+
+# alias -> canonical name
+METRIC_ALIASES: Dict[str, str] = {
+    "euclidean": "euclidean", "l2": "euclidean",
+    "sqeuclidean": "sqeuclidean",
+    "cosine": "cosine",
+    "correlation": "correlation",
+    "hellinger": "hellinger",
+    "manhattan": "manhattan", "l1": "manhattan", "cityblock": "manhattan",
+    "taxicab": "manhattan",
+    "chebyshev": "chebyshev", "linf": "chebyshev",
+    "minkowski": "minkowski",
+    "canberra": "canberra",
+    "hamming": "hamming",
+}
+# per-coordinate reductions served by the `pairwise_dist` kernel -> its op code
+TILE_OPS: Dict[str, int] = {
+    "manhattan": 0, "chebyshev": 1, "minkowski": 2, "canberra": 3, "hamming": 4,
+}
+
+
+def resolve_metric(metric: str, p: float = 2.0) -> Tuple[str, float]:
+    """(canonical metric, p) of a metric name or alias. minkowski with p = 1
+    and p = 2 resolves to manhattan and euclidean. ValueError for jaccard
+    (dense inputs), an unknown name, or a p that is not finite and > 0."""
+    name = str(metric).lower()
+    if name == "jaccard":
+        raise ValueError("Metric 'jaccard' not supported for dense inputs.")
+    if name not in METRIC_ALIASES:
+        raise ValueError(
+            f"Unknown metric {metric!r}; accepted: {', '.join(sorted(METRIC_ALIASES))}"
+        )
+    name = METRIC_ALIASES[name]
+    if name != "minkowski":
+        return name, 2.0
+    p = float(p)
+    if not (math.isfinite(p) and p > 0):
+        raise ValueError(f"minkowski p must be finite and > 0, got {p!r}")
+    if p == 1.0:
+        return "manhattan", 2.0
+    if p == 2.0:
+        return "euclidean", 2.0
+    return name, p
+
+
+def knn_topk_metric(
+    Q: torch.Tensor,
+    I: torch.Tensor,
+    k: int,
+    metric: str = "euclidean",
+    p: float = 2.0,
+    chunk_elems: int = 1 << 29,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(dists f32 [q,k] ascending, idx int64 [q,k]) of queries against items
+    under `metric` (any name of METRIC_ALIASES; `p` for minkowski).
+
+    euclidean is `knn_topk`, verbatim. On the GPU the GEMM family (sqeuclidean,
+    cosine, correlation, hellinger) preprocesses the rows in torch and reuses
+    library GEMM + `knn_merge_topk`; the tile family (manhattan, chebyshev,
+    minkowski, canberra, hamming) runs the `pairwise_dist` kernel per item
+    chunk + `knn_merge_topk_keys`, the root / division by d applied to the k
+    survivors only. CPU tensors, k > 64 and non-f32 input take the chunked
+    torch path."""
+    metric, p = resolve_metric(metric, p)
+    if metric == "euclidean":
+        return knn_topk(Q, I, k)
+    kernel_path = (
+        use_hip(Q, I)
+        and k <= min(64, I.shape[0])
+        and Q.dtype == torch.float32
+        and I.dtype == torch.float32
+        and Q.shape[0] > 0
     )
+    if not kernel_path:
+        return torch_ref.knn_topk_metric(Q, I, k, metric, p)
+    if metric in TILE_OPS:
+        keys, idx = _tile_select_keys(
+            Q.contiguous(), I.contiguous(), k, TILE_OPS[metric], p, chunk_elems
+        )
+    elif metric == "sqeuclidean":
+        Q, I = Q.contiguous(), I.contiguous()
+        q_sq = (Q * Q).sum(dim=1).contiguous()
+        i_sq = (I * I).sum(dim=1).contiguous()
+        keys, idx = _gemm_select_keys(Q, I, q_sq, i_sq, k, chunk_elems)
+    else:
+        # key = 1 - <q', i'>: q_sq = 1, i_sq = 0 and the query rows halved
+        # (exact) so that knn_merge_topk's -2*dot is -<q', i'>
+        Qp = (torch_ref.metric_rows(Q, metric) * 0.5).contiguous()
+        Ip = torch_ref.metric_rows(I, metric).contiguous()
+        q_sq = torch.ones(Q.shape[0], dtype=torch.float32, device=Q.device)
+        i_sq = torch.zeros(I.shape[0], dtype=torch.float32, device=Q.device)
+        keys, idx = _gemm_select_keys(Qp, Ip, q_sq, i_sq, k, chunk_elems)
+    return torch_ref.finish_keys(keys, metric, p, I.shape[1]), idx
+
+
+def _tile_select_keys(
+    Q: torch.Tensor, I: torch.Tensor, k: int, op: int, p: float, chunk_elems: int
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """k smallest `pairwise_dist` keys per row, chunked as the GEMM path is."""
+    ext = hip_ops()
+
+    def merge_chunk(Gv, s, e, best_d, best_i):
+        ext.pairwise_dist(Q, I[s:e], op, float(p), Gv)
+        ext.knn_merge_topk_keys(Gv, s, best_d, best_i)
+
+    return _chunked_select(Q.shape[0], I.shape[0], k, Q.device, chunk_elems, merge_chunk)

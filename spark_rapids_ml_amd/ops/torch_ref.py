@@ -127,6 +127,142 @@ def knn_topk(
     return dists, idx
 
 
+# metrics that are per-coordinate reductions (no GEMM form) and the ones that
+# reduce to a dot product of preprocessed rows; canonical names only, the
+# alias table lives in ops/knn.py
+TILE_METRICS = ("manhattan", "chebyshev", "minkowski", "canberra", "hamming")
+GEMM_METRICS = ("sqeuclidean", "cosine", "correlation", "hellinger")
+
+
+def metric_rows(X: torch.Tensor, metric: str) -> torch.Tensor:
+    """Rows preprocessed so that a GEMM-family distance is 1 - <x', y'>:
+    unit rows (cosine), centred unit rows (correlation), sqrt rows (hellinger).
+    Raises ValueError where the metric is undefined for a row."""
+    if metric == "hellinger":
+        if bool((X < 0).any()):
+            raise ValueError("metric='hellinger' requires non-negative inputs")
+        return torch.sqrt(X)
+    if metric == "correlation":
+        X = X - X.mean(dim=1, keepdim=True)
+    elif metric != "cosine":
+        raise ValueError(f"metric {metric!r} has no row transform")
+    norm = torch.sqrt((X * X).sum(dim=1, keepdim=True))
+    if bool((norm == 0).any()):
+        what = "zero-norm rows" if metric == "cosine" else "constant rows"
+        raise ValueError(f"metric={metric!r} is undefined for {what}")
+    # a true division: scaling a row by 2^j scales its norm by exactly 2^j,
+    # so the unit row is bit-identical
+    return X / norm
+
+
+def _tile_keys(Q: torch.Tensor, I: torch.Tensor, metric: str, p: float) -> torch.Tensor:
+    """[q, n] monotone keys of a tile metric (sum, max, sum |.|^p, mismatch
+    count) through a [q, n, d] broadcast; the caller bounds q * n * d."""
+    if metric == "hamming":
+        return (Q[:, None, :] != I[None, :, :]).sum(dim=2).to(torch.float32)
+    diff = (Q[:, None, :] - I[None, :, :]).abs()
+    if metric == "manhattan":
+        return diff.sum(dim=2)
+    if metric == "chebyshev":
+        return diff.amax(dim=2)
+    if metric == "minkowski":
+        return (diff ** p).sum(dim=2)
+    if metric == "canberra":
+        den = Q.abs()[:, None, :] + I.abs()[None, :, :]
+        return torch.where(den > 0, diff / den, torch.zeros_like(diff)).sum(dim=2)
+    raise ValueError(f"unknown tile metric {metric!r}")
+
+
+def finish_keys(keys: torch.Tensor, metric: str, p: float, d: int) -> torch.Tensor:
+    """Monotone keys -> distances (applied to the k survivors only)."""
+    if metric == "minkowski":
+        return keys ** (1.0 / p)
+    if metric == "hamming":
+        # in f64: a division by a host scalar may run as a multiplication by
+        # its reciprocal, which in f32 is not the correctly rounded count / d
+        return (keys.to(torch.float64) / float(d)).to(torch.float32)
+    if metric in ("cosine", "correlation", "sqeuclidean"):
+        return torch.clamp(keys, min=0.0)
+    if metric == "hellinger":
+        return torch.sqrt(torch.clamp(keys, min=0.0))
+    return keys
+
+
+def _metric_keys(Q: torch.Tensor, I: torch.Tensor, metric: str, p: float,
+                 block_elems: int = 1 << 24) -> torch.Tensor:
+    """[q, n] keys of PREPROCESSED rows; the [rows, n, d] intermediate of the
+    tile metrics is bounded by block_elems."""
+    if metric == "sqeuclidean":
+        return pairwise_sq_dists(Q, I)
+    if metric in GEMM_METRICS:
+        return 1.0 - Q @ I.T
+    n, d = I.shape[0], max(1, I.shape[1])
+    rows = max(1, block_elems // max(1, n * d))
+    out = torch.empty((Q.shape[0], n), dtype=torch.float32, device=Q.device)
+    for s in range(0, Q.shape[0], rows):
+        out[s:s + rows] = _tile_keys(Q[s:s + rows], I, metric, p)
+    return out
+
+
+def pairwise_distances(
+    Q: torch.Tensor, I: torch.Tensor, metric: str = "euclidean", p: float = 2.0
+) -> torch.Tensor:
+    """[q, n] f32 distances under a canonical metric name (scipy cdist
+    definitions; hellinger is sqrt(max(0, 1 - sum sqrt(x_i y_i))))."""
+    if metric == "euclidean":
+        return torch.sqrt(pairwise_sq_dists(Q, I))
+    if metric in ("cosine", "correlation", "hellinger"):
+        Q, I = metric_rows(Q, metric), metric_rows(I, metric)
+    elif metric not in TILE_METRICS and metric != "sqeuclidean":
+        raise ValueError(f"unknown metric {metric!r}")
+    return finish_keys(_metric_keys(Q, I, metric, p), metric, p, I.shape[1])
+
+
+def knn_topk_metric(
+    Q: torch.Tensor,
+    I: torch.Tensor,
+    k: int,
+    metric: str = "euclidean",
+    p: float = 2.0,
+    block_elems: int = 1 << 24,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Brute-force kNN under a canonical metric: (dists [q,k] ascending, idx
+    int64 [q,k]). Queries and items are both chunked with a running top-k
+    merge, so no block larger than block_elems elements ([q, n] for the GEMM
+    family, [q, n, d] for the tile family) is ever materialized."""
+    if metric == "euclidean":
+        return knn_topk(Q, I, k)
+    if metric in ("cosine", "correlation", "hellinger"):
+        Q, I = metric_rows(Q, metric), metric_rows(I, metric)
+    elif metric not in TILE_METRICS and metric != "sqeuclidean":
+        raise ValueError(f"unknown metric {metric!r}")
+    nq, ni, d = Q.shape[0], I.shape[0], I.shape[1]
+    k = min(k, ni)
+    per_pair = max(1, d) if metric in TILE_METRICS else 1
+    ichunk = max(k, min(ni, 4096))
+    qchunk = max(1, block_elems // (ichunk * per_pair))
+    dists = torch.empty((nq, k), dtype=torch.float32, device=Q.device)
+    idx = torch.empty((nq, k), dtype=torch.int64, device=Q.device)
+    for s in range(0, nq, qchunk):
+        e = min(nq, s + qchunk)
+        best_d = best_i = None
+        for s2 in range(0, ni, ichunk):
+            e2 = min(ni, s2 + ichunk)
+            keys = _metric_keys(Q[s:e], I[s2:e2], metric, p, block_elems)
+            vals, ids = torch.topk(keys, min(k, e2 - s2), dim=1, largest=False)
+            ids = ids + s2
+            if best_d is not None:
+                vals = torch.cat([best_d, vals], dim=1)
+                ids = torch.cat([best_i, ids], dim=1)
+                vals, order = torch.topk(vals, min(k, vals.shape[1]), dim=1, largest=False)
+                ids = ids.gather(1, order)
+            best_d, best_i = vals, ids
+        best_d, order = torch.sort(best_d, dim=1)
+        dists[s:e] = finish_keys(best_d, metric, p, d)
+        idx[s:e] = best_i.gather(1, order)
+    return dists, idx
+
+
 def softmax_residual(
     scores: torch.Tensor, y_idx: torch.Tensor
 ) -> Tuple[torch.Tensor, torch.Tensor]:

@@ -48,6 +48,24 @@ reference).
 
 Any other DBSCAN metric raises `ValueError` at `transform`.
 
+`UMAP(metric=..., metric_kwds={"p": ...})` (reference umap.py metric list). Only the kNN stage of fit and transform depends on the metric; a fitted model keeps its estimator's `metric` / `metric_kwds` (also through save / load) and transforms with them. All errors are `ValueError`.
+
+| metric (aliases) | distance | kNN path on the GPU | `build_algo="nn_descent"` |
+|---|---|---|---|
+| `euclidean` (`l2`) | √Σ(x−y)² | library GEMM + `knn_merge_topk` (unchanged) | yes |
+| `sqeuclidean` | Σ(x−y)² | same, no final sqrt | yes |
+| `cosine` | 1 − x·y/(‖x‖‖y‖) | GEMM on unit rows; a zero-norm row raises | yes, on the unit rows |
+| `correlation` | cosine of the mean-centred rows | GEMM; a constant row raises | yes, on the centred unit rows |
+| `hellinger` | √max(0, 1 − Σ√(xᵢyᵢ)) | GEMM on √x rows; a negative entry raises | raises |
+| `manhattan` (`l1`, `cityblock`, `taxicab`) | Σ\\|x−y\\| | `pairwise_dist` + `knn_merge_topk_keys` | raises |
+| `chebyshev` (`linf`) | max\\|x−y\\| | same | raises |
+| `minkowski` | (Σ\\|x−y\\|ᵖ)^(1/p), `p` from `metric_kwds` (default 2; finite and > 0; 1 and 2 resolve to manhattan and euclidean) | same | raises |
+| `canberra` | Σ\\|x−y\\|/(\\|x\\|+\\|y\\|), 0/0 = 0 | same | raises |
+| `hamming` | (#coordinates with xᵢ≠yᵢ)/d | same | raises |
+| `jaccard` | — | raises `Metric 'jaccard' not supported for dense inputs.` (there is no sparse UMAP input) | — |
+
+Under `build_algo="auto"` the per-coordinate metrics and hellinger build the graph by brute force at any size; the L2-reducible ones switch to nn-descent above 50 000 rows as euclidean does. An unknown name raises and lists the accepted names.
+
 ## Evaluators
 
 `RegressionEvaluator` (rmse|mse|r2|mae|var), `MulticlassClassificationEvaluator` \
