@@ -2178,6 +2178,135 @@ __global__ __launch_bounds__(256) void pairwise_dist_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// csr_pairwise: one [nq, c] block of distance KEYS of CSR query rows against
+// an item chunk given in CSC (per column: the chunk-local item rows holding
+// it, and their values). It is pairwise_dist's sparse sibling and feeds
+// knn_merge_topk_keys the same way.
+//
+// Every metric served has f(0,0) = 0, so
+//   key(q,x) = A_q + B_x + sum_{j in nz(q) & nz(x)} t(q_j, x_j)
+// with A_q = sum_j f(q_j,0) and B_x = sum_j f(0,x_j) computed once by the
+// caller and t(v,w) = f(v,w) - f(v,0) - f(0,w). Only the intersection is
+// walked, Gustavson style: for each nonzero (j, v) of the query row, for each
+// (i, w) of column j, acc[i] += t(v, w).
+//
+// One wave owns one query row (4 rows per block) and keeps the row's acc[c]
+// in LDS: zeroed, accumulated, then finished and written to out[row, :] in
+// one coalesced pass. The wave takes its row's nonzeros IN ORDER and spreads
+// its lanes over the column list: within one nonzero all targets are
+// distinct, and nonzeros are sequential, so there are no atomics and the
+// f32 sum of every pair has one fixed order (bit-reproducible).
+// The row's nonzeros are fetched 64 at a time, one per lane with their column
+// bounds, and handed round by shuffles: the colptr lookups of a batch are in
+// flight together rather than chained one per nonzero. The batch loops have
+// wave-uniform bounds (see knn_merge_topk_kernel); the per-lane loop over a
+// column list holds no cross-lane operation.
+// Lane use is c*density/64 of a wave when column lists are short: the kernel
+// is latency-bound there (profiles/README.md).
+// ---------------------------------------------------------------------------
+
+constexpr int CP_CHUNK = 8192;  // 4 rows x 8192 f32 = 128 KB of LDS per block
+
+enum { CP_DOT = 0, CP_L1 = 1, CP_LP = 2, CP_CANBERRA = 3, CP_HAMMING = 4, CP_JACCARD = 5 };
+
+template <int OP>
+__device__ inline float cp_term(float v, float w, float p) {
+  if constexpr (OP == CP_DOT) {
+    return v * w;
+  } else if constexpr (OP == CP_L1) {
+    return fabsf(v - w) - fabsf(v) - fabsf(w);
+  } else if constexpr (OP == CP_LP) {
+    // the exp2/log2 form of pd_accum; v == w gives 2^-inf = 0
+    return __builtin_amdgcn_exp2f(p * __builtin_amdgcn_logf(fabsf(v - w))) -
+           __builtin_amdgcn_exp2f(p * __builtin_amdgcn_logf(fabsf(v))) -
+           __builtin_amdgcn_exp2f(p * __builtin_amdgcn_logf(fabsf(w)));
+  } else if constexpr (OP == CP_CANBERRA) {
+    // stored values are nonzero, so the denominator is positive
+    return __fdiv_rn(fabsf(v - w), fabsf(v) + fabsf(w)) - 2.0f;
+  } else if constexpr (OP == CP_HAMMING) {
+    return (v != w ? 1.0f : 0.0f) - 2.0f;
+  } else {
+    return 1.0f;
+  }
+}
+
+template <int OP>
+__device__ inline float cp_finish(float a, float b, float acc) {
+  if constexpr (OP == CP_DOT) {
+    return a + b - 2.0f * acc;
+  } else if constexpr (OP == CP_JACCARD) {
+    // 1 - acc / (u - acc) with u = nnz(q) + nnz(x), the union being u - acc,
+    // as one quotient of exact integers: a single rounding
+    const float u = a + b;
+    return u > 0.0f ? __fdiv_rn(u - 2.0f * acc, u - acc) : 0.0f;
+  } else {
+    return a + b + acc;
+  }
+}
+
+// LDS accesses of one wave execute in order; this only keeps the compiler
+// from moving one nonzero's read-modify-writes across the next one's
+__device__ inline void cp_wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+template <int OP>
+__global__ __launch_bounds__(256) void csr_pairwise_kernel(
+    const int64_t* __restrict__ q_indptr,  // [nq + 1]
+    const int32_t* __restrict__ q_col,     // [nnz_q] column ids
+    const float* __restrict__ q_val,       // [nnz_q]
+    const int64_t* __restrict__ colptr,    // [d + 1] CSC of the item chunk
+    const int32_t* __restrict__ c_row,     // [nnz_c] chunk-local item rows
+    const float* __restrict__ c_val,       // [nnz_c]
+    const float* __restrict__ A,           // [nq]
+    const float* __restrict__ B,           // [c]
+    int64_t nq, int c, int d, float p,
+    float* __restrict__ out) {             // [nq, c]
+  extern __shared__ float cp_acc[];  // [4][c]
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int64_t row = (int64_t)blockIdx.x * 4 + wave;
+  // before any indptr read; the waves of a block share no barrier below
+  if (row >= nq) return;
+
+  float* acc = cp_acc + (size_t)wave * c;
+  for (int i = lane; i < c; i += 64) acc[i] = 0.0f;
+  cp_wave_sync();
+
+  const int64_t qs = q_indptr[row];
+  const int64_t qe = q_indptr[row + 1];
+  for (int64_t t0 = qs; t0 < qe; t0 += 64) {
+    const int nb = (int)min((int64_t)64, qe - t0);  // wave-uniform
+    float v_l = 0.0f;
+    int cs_l = 0, ce_l = 0;
+    if (lane < nb) {
+      const int j = q_col[t0 + lane];
+      v_l = q_val[t0 + lane];
+      if ((unsigned)j < (unsigned)d) {  // nnz_c < 2^31 is checked on the host
+        cs_l = (int)colptr[j];
+        ce_l = (int)colptr[j + 1];
+      }
+    }
+    for (int u = 0; u < nb; ++u) {
+      const float v = __shfl(v_l, u, 64);
+      const int cs = __shfl(cs_l, u, 64);
+      const int ce = __shfl(ce_l, u, 64);
+      for (int e = cs + lane; e < ce; e += 64) {
+        const int i = c_row[e];
+        if ((unsigned)i < (unsigned)c) acc[i] += cp_term<OP>(v, c_val[e], p);
+      }
+      cp_wave_sync();
+    }
+  }
+
+  const float a = A[row];
+  float* o = out + row * c;
+  for (int i = lane; i < c; i += 64) o[i] = cp_finish<OP>(a, B[i], acc[i]);
+}
+
+// ---------------------------------------------------------------------------
 // gather_dists: d2[i][j] = ||A[i] - B[cand[i][j]]||^2 — the nn-descent /
 // beam-search hot op (per-row private candidate lists make this a gathered
 // row-vs-rows reduction, not a GEMM). One wave per output row: A[i] is
@@ -3156,6 +3285,67 @@ void pairwise_dist(torch::Tensor Q, torch::Tensor I, int64_t op, double p, torch
   C10_HIP_KERNEL_LAUNCH_CHECK();
 }
 
+template <int OP>
+static void csr_pairwise_launch(unsigned grid, size_t lds, const int64_t* q_indptr,
+                                const int32_t* q_col, const float* q_val, const int64_t* colptr,
+                                const int32_t* c_row, const float* c_val, const float* A,
+                                const float* B, int64_t nq, int c, int d, float p, float* out) {
+  hipLaunchKernelGGL(csr_pairwise_kernel<OP>, dim3(grid), dim3(256), lds, cur_stream(), q_indptr,
+                     q_col, q_val, colptr, c_row, c_val, A, B, nq, c, d, p, out);
+}
+
+// op: 0 dot (A + B - 2 acc), 1 L1, 2 Lp (no root), 3 canberra, 4 hamming
+// (mismatch count), 5 jaccard (distance). Queries in CSR, the item chunk in
+// CSC with chunk-local rows; A [nq] and B [c] are the per-row constants.
+void csr_pairwise(torch::Tensor q_indptr, torch::Tensor q_col, torch::Tensor q_val,
+                  torch::Tensor colptr, torch::Tensor c_row, torch::Tensor c_val, torch::Tensor A,
+                  torch::Tensor B, int64_t op, double p, torch::Tensor out) {
+  const torch::Tensor* all[] = {&q_indptr, &q_col, &q_val, &colptr, &c_row, &c_val, &A, &B, &out};
+  for (const torch::Tensor* t : all)
+    TORCH_CHECK(t->is_cuda() && t->device() == out.device() && t->is_contiguous(),
+                "csr_pairwise tensors must be contiguous and on one device");
+  TORCH_CHECK(q_indptr.dtype() == torch::kInt64 && colptr.dtype() == torch::kInt64,
+              "indptr and colptr must be int64");
+  TORCH_CHECK(q_col.dtype() == torch::kInt32 && c_row.dtype() == torch::kInt32,
+              "column and row indices must be int32");
+  TORCH_CHECK(q_val.dtype() == torch::kFloat32 && c_val.dtype() == torch::kFloat32 &&
+                  A.dtype() == torch::kFloat32 && B.dtype() == torch::kFloat32 &&
+                  out.dtype() == torch::kFloat32,
+              "values, A, B and out must be float32");
+  TORCH_CHECK(q_indptr.dim() == 1 && q_indptr.size(0) >= 1 && colptr.dim() == 1 &&
+              colptr.size(0) >= 1 && A.dim() == 1 && B.dim() == 1 && out.dim() == 2);
+  const int64_t nq = q_indptr.size(0) - 1;
+  const int64_t c = B.size(0);
+  const int64_t d = colptr.size(0) - 1;
+  TORCH_CHECK(A.size(0) == nq, "A must be [nq]");
+  TORCH_CHECK(c <= CP_CHUNK, "csr_pairwise chunk is limited to ", CP_CHUNK, " items by LDS");
+  TORCH_CHECK(out.size(0) == nq && out.size(1) == c, "out must be [nq, c]");
+  TORCH_CHECK(d < (int64_t(1) << 31), "csr_pairwise supports d < 2^31");
+  TORCH_CHECK(q_col.numel() == q_val.numel() && c_row.numel() == c_val.numel());
+  TORCH_CHECK(c_row.numel() < (int64_t(1) << 31), "csr_pairwise chunk nnz must be < 2^31");
+  TORCH_CHECK(op >= CP_DOT && op <= CP_JACCARD, "unknown csr_pairwise op");
+  TORCH_CHECK(op != CP_LP || (std::isfinite(p) && p > 0.0), "minkowski p must be finite and > 0");
+  if (nq == 0 || c == 0) return;
+  TORCH_CHECK((nq + 3) / 4 < (int64_t(1) << 31), "csr_pairwise block is too large");
+  const unsigned grid = (unsigned)((nq + 3) / 4);
+  const size_t lds = (size_t)4 * (size_t)c * sizeof(float);
+#define CP_ARGS                                                                                  \
+  grid, lds, q_indptr.data_ptr<int64_t>(), q_col.data_ptr<int32_t>(), q_val.data_ptr<float>(),   \
+      colptr.data_ptr<int64_t>(), c_row.data_ptr<int32_t>(), c_val.data_ptr<float>(),            \
+      A.data_ptr<float>(), B.data_ptr<float>(), nq, (int)c, (int)d, (float)p,                    \
+      out.data_ptr<float>()
+  switch (op) {
+    case CP_DOT: csr_pairwise_launch<CP_DOT>(CP_ARGS); break;
+    case CP_L1: csr_pairwise_launch<CP_L1>(CP_ARGS); break;
+    case CP_LP: csr_pairwise_launch<CP_LP>(CP_ARGS); break;
+    case CP_CANBERRA: csr_pairwise_launch<CP_CANBERRA>(CP_ARGS); break;
+    case CP_HAMMING: csr_pairwise_launch<CP_HAMMING>(CP_ARGS); break;
+    default: csr_pairwise_launch<CP_JACCARD>(CP_ARGS); break;
+  }
+#undef CP_ARGS
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+}
+
 torch::Tensor gather_dists(torch::Tensor A, torch::Tensor B, torch::Tensor cand) {
   TORCH_CHECK(A.is_cuda() && A.dtype() == torch::kFloat32 && A.is_contiguous());
   TORCH_CHECK(B.dtype() == torch::kFloat32 && B.is_contiguous());
@@ -3366,6 +3556,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "running top-k merge over a block of distance keys");
   m.def("pairwise_dist", &pairwise_dist,
         "register-tiled all-pairs distance keys (L1, Linf, Lp, canberra, hamming)");
+  m.def("csr_pairwise", &csr_pairwise,
+        "[nq, c] distance keys of CSR queries against a CSC item chunk");
   m.def("gather_dists", &gather_dists, "gathered row-vs-candidates squared distances");
   m.def("ivf_scan_topk", &ivf_scan_topk, "fused IVF-Flat probed-list scan + running top-k");
   m.attr("_is_hip") = true;

@@ -17,9 +17,10 @@ import numpy as np
 import torch
 
 from ..core import Estimator, Model, _FitContext
-from ..data import to_device_tensor
+from ..data import _is_sparse, to_device_tensor
 from ..params import (
     DictTypeConverters,
+    HasEnableSparseDataOptim,
     HasFeaturesCol,
     HasFeaturesCols,
     HasLabelCol,
@@ -27,7 +28,7 @@ from ..params import (
     Param,
     TypeConverters,
 )
-from ..ops.knn import knn_topk, knn_topk_metric, resolve_metric
+from ..ops.knn import knn_topk, knn_topk_metric, knn_topk_metric_sparse, resolve_metric
 from ..ops import torch_ref
 from ..utils import as_numpy
 
@@ -323,7 +324,9 @@ def _optimize_embedding(
     return emb
 
 
-class _UMAPParams(HasFeaturesCol, HasFeaturesCols, HasLabelCol, HasOutputCol):
+class _UMAPParams(
+    HasFeaturesCol, HasFeaturesCols, HasLabelCol, HasOutputCol, HasEnableSparseDataOptim
+):
     n_neighbors = Param("umap", "n_neighbors", "kNN graph size.", TypeConverters.toFloat)
     n_components = Param("umap", "n_components", "embedding dim.", TypeConverters.toInt)
     n_epochs = Param("umap", "n_epochs", "SGD epochs (0=auto).", TypeConverters.toInt)
@@ -345,7 +348,8 @@ class _UMAPParams(HasFeaturesCol, HasFeaturesCols, HasLabelCol, HasOutputCol):
         "umap", "metric",
         "distance metric of the kNN graph: l1/cityblock/taxicab/manhattan, "
         "euclidean/l2, sqeuclidean, canberra, minkowski, chebyshev/linf, cosine, "
-        "correlation, hellinger, hamming (jaccard needs sparse input: unsupported).",
+        "correlation, hellinger, hamming; jaccard for sparse (CSR) input only. "
+        "Sparse input takes every name but chebyshev/linf and correlation.",
         TypeConverters.toString,
     )
     metric_kwds = Param(
@@ -393,10 +397,18 @@ class _UMAPParams(HasFeaturesCol, HasFeaturesCols, HasLabelCol, HasOutputCol):
             outputCol="embedding",
         )
 
-    def _metric(self) -> Tuple[str, float]:
-        """(canonical metric, p) from `metric` and `metric_kwds`."""
+    def _metric(self, sparse: bool = False) -> Tuple[str, float]:
+        """(canonical metric, p) from `metric` and `metric_kwds`, under the
+        rules of dense or of sparse input."""
         kwds = self.getOrDefault("metric_kwds") or {}
-        return resolve_metric(self.getOrDefault("metric"), kwds.get("p", 2.0))
+        return resolve_metric(self.getOrDefault("metric"), kwds.get("p", 2.0), sparse=sparse)
+
+    def _sparse_optim(self) -> Optional[bool]:
+        """enable_sparse_data_optim: None = follow the input, True = require
+        CSR, False = densify (reference params.py:45-66)."""
+        if self.isSet("enable_sparse_data_optim"):
+            return self.getOrDefault("enable_sparse_data_optim")
+        return None
 
     @classmethod
     def _param_mapping(cls) -> Dict[str, Optional[str]]:
@@ -411,8 +423,9 @@ class _UMAPParams(HasFeaturesCol, HasFeaturesCols, HasLabelCol, HasOutputCol):
     @classmethod
     def _param_value_mapping(cls):
         def _metric(v):
-            # jaccard is a documented name: it passes here and reaches the
-            # dense-input error at fit; an unknown name lists the accepted ones
+            # jaccard is a documented name: it passes here and, on dense
+            # input, reaches the dense-input error at fit; an unknown name
+            # lists the accepted ones
             if str(v).lower() != "jaccard":
                 resolve_metric(v)
             return v
@@ -468,6 +481,54 @@ class UMAP(_UMAPParams, Estimator):
         # supervised fit when a labelCol is present (reference umap.py:1035-1050)
         return self.isSet("labelCol")
 
+    # CSR features stay CSR (reference umap.py:901-903, 955-982) unless
+    # enable_sparse_data_optim=False asks for the dense path
+    _supports_sparse = True
+
+    def _extract_xy(self, df: Any) -> Tuple[Any, Optional[np.ndarray]]:
+        X, y = super()._extract_xy(df)
+        opt = self._sparse_optim()
+        if _is_sparse(X):
+            if opt is False:
+                X = np.asarray(X.todense()).astype(
+                    np.float32 if self._float32_inputs else np.float64
+                )
+            else:
+                X = X.tocsr()
+        elif opt is True:
+            raise ValueError("enable_sparse_data_optim=True requires sparse CSR features")
+        return X, y
+
+    def _gather_csr(self, X: Any, y: Optional[np.ndarray], ctx: _FitContext, rng: Any):
+        """(sampled CSR rows of all ranks stacked in rank order, their labels):
+        per-row nnz, column ids and values travel through allgather_rows and
+        indptr is rebuilt from the counts."""
+        import scipy.sparse as sp
+
+        comm = ctx.comm
+        frac = float(self.getOrDefault("sample_fraction"))
+        X_local = X.astype(np.float32)
+        y_local = np.asarray(y, dtype=np.float32) if y is not None else None
+        if frac < 1.0 and X_local.shape[0] > 0:
+            m = max(1, int(frac * X_local.shape[0]))
+            sel = rng.choice(X_local.shape[0], m, replace=False)
+            X_local = X_local[sel]
+            if y_local is not None:
+                y_local = y_local[sel]
+        dev = comm._coll_device()
+
+        def gather(a: np.ndarray) -> np.ndarray:
+            parts = comm.allgather_rows(torch.from_numpy(np.ascontiguousarray(a)).to(dev))
+            return np.concatenate([p.cpu().numpy() for p in parts])
+
+        counts = gather(np.diff(X_local.indptr).astype(np.int64))
+        indices = gather(X_local.indices.astype(np.int32))
+        data = gather(X_local.data.astype(np.float32))
+        indptr = np.concatenate([np.zeros(1, dtype=np.int64), np.cumsum(counts)])
+        X_fit = sp.csr_matrix((data, indices, indptr), shape=(counts.shape[0], ctx.pdesc.n))
+        y_fit = gather(y_local) if y_local is not None else None
+        return X_fit, y_fit
+
     def _fit_array(
         self, X: Any, y: Optional[Any], ctx: _FitContext, params: Dict[str, Any]
     ) -> Dict[str, Any]:
@@ -475,6 +536,9 @@ class UMAP(_UMAPParams, Estimator):
         frac = float(self.getOrDefault("sample_fraction"))
         seed = int(self.getOrDefault("random_state"))
         rng = np.random.default_rng(seed)
+        if _is_sparse(X):
+            X_fit, y_fit = self._gather_csr(X, y, ctx, rng)
+            return self._fit_gathered(X_fit, y_fit, ctx)
         X_local = np.ascontiguousarray(X, dtype=np.float32)
         y_local = np.asarray(y, dtype=np.float32) if y is not None else None
         if frac < 1.0 and X_local.shape[0] > 0:
@@ -494,7 +558,14 @@ class UMAP(_UMAPParams, Estimator):
                 torch.from_numpy(y_local).to(comm._coll_device())
             )
             y_fit = np.concatenate([p.cpu().numpy() for p in y_parts])
+        return self._fit_gathered(X_fit, y_fit, ctx)
 
+    def _fit_gathered(
+        self, X_fit: Any, y_fit: Optional[np.ndarray], ctx: _FitContext
+    ) -> Dict[str, Any]:
+        """Rank 0 fits the gathered rows (dense array or CSR); the embedding
+        is broadcast. Every rank holds the same X_fit already."""
+        comm = ctx.comm
         if comm.rank == 0:
             emb = self._fit_single(X_fit, ctx.device, y_fit)
         else:
@@ -507,7 +578,7 @@ class UMAP(_UMAPParams, Estimator):
 
         return {
             "embedding_": emb.astype(np.float32),
-            "raw_data_": X_fit.astype(np.float32),
+            "raw_data_": X_fit if _is_sparse(X_fit) else X_fit.astype(np.float32),
             "a_": self._ab()[0],
             "b_": self._ab()[1],
         }
@@ -522,7 +593,7 @@ class UMAP(_UMAPParams, Estimator):
         return float(a), float(b)
 
     def _fit_single(
-        self, X: np.ndarray, device: torch.device, y: Optional[np.ndarray] = None
+        self, X: Any, device: torch.device, y: Optional[np.ndarray] = None
     ) -> np.ndarray:
         import os as _os
         import time as _time
@@ -544,9 +615,15 @@ class UMAP(_UMAPParams, Estimator):
         k = min(k, max(2, n - 1))
         dim = int(self.getOrDefault("n_components"))
         seed = int(self.getOrDefault("random_state"))
-        Xt = to_device_tensor(X, device)
-        metric, p = self._metric()
+        sparse = _is_sparse(X)
+        metric, p = self._metric(sparse)
         build_algo = str(self.getOrDefault("build_algo") or "auto").lower()
+        if sparse and build_algo == "nn_descent":
+            raise ValueError(
+                "build_algo='nn_descent' is not supported for sparse input: "
+                "use 'brute_force_knn' or 'auto'"
+            )
+        Xt = None if sparse else to_device_tensor(X, device)
         # nn-descent works in L2 (the reference states it supports only L2):
         # cosine / correlation qualify on their transformed rows, the tile
         # metrics and hellinger always build by brute force
@@ -561,8 +638,12 @@ class UMAP(_UMAPParams, Estimator):
             build_algo == "brute_force_knn"
             or (build_algo == "auto" and n <= 50000)
             or not l2_rows
+            or sparse
         )
-        if brute and metric == "euclidean":
+        if sparse:
+            # CSR rows: the csr_pairwise kernel walks stored entries only
+            d, i = knn_topk_metric_sparse(X, X, k + 1, metric, p, device=device)
+        elif brute and metric == "euclidean":
             d, i = knn_topk(Xt, Xt, k + 1)
         elif brute:
             d, i = knn_topk_metric(Xt, Xt, k + 1, metric, p)
@@ -584,7 +665,7 @@ class UMAP(_UMAPParams, Estimator):
                 vals = torch.sqrt(vals)
             d = torch.cat([torch.zeros(n, 1, device=Xt.device), vals[:, :k]], dim=1)
         _t0 = _mark("knn_graph", _t0)
-        if metric == "euclidean" or not brute:
+        if (metric == "euclidean" and not sparse) or not brute:
             knn_d_t = d[:, 1:].contiguous()  # drop self column
             knn_i_t = i[:, 1:].contiguous()
         else:
@@ -678,24 +759,60 @@ class UMAPModel(_UMAPParams, Model):
     def __init__(
         self,
         embedding_: np.ndarray,
-        raw_data_: np.ndarray,
+        raw_data_: Any = None,
         a_: float = 1.577,
         b_: float = 0.895,
+        raw_data_indptr: Optional[np.ndarray] = None,
+        raw_data_indices: Optional[np.ndarray] = None,
+        raw_data_data: Optional[np.ndarray] = None,
+        raw_data_shape: Optional[np.ndarray] = None,
         **kwargs: Any,
     ) -> None:
+        if raw_data_ is None:
+            # a sparse model as persisted: the CSR's three arrays + its shape
+            import scipy.sparse as sp
+
+            if raw_data_indptr is None or raw_data_indices is None or raw_data_data is None \
+                    or raw_data_shape is None:
+                raise ValueError(
+                    "UMAPModel needs raw_data_ or the four raw_data_{indptr,indices,data,shape}"
+                )
+            raw_data_ = sp.csr_matrix(
+                (np.asarray(raw_data_data), np.asarray(raw_data_indices),
+                 np.asarray(raw_data_indptr)),
+                shape=tuple(int(v) for v in np.asarray(raw_data_shape)),
+            )
+        elif _is_sparse(raw_data_):
+            raw_data_ = raw_data_.tocsr()
+        else:
+            raw_data_ = np.asarray(raw_data_)
         super().__init__(
             embedding_=np.asarray(embedding_),
-            raw_data_=np.asarray(raw_data_),
+            raw_data_=raw_data_,
             a_=float(a_),
             b_=float(b_),
         )
+
+    def _get_model_attributes(self) -> Dict[str, Any]:
+        """A CSR raw_data_ is handed to the npz writer as its arrays."""
+        attrs = dict(self._model_attributes)
+        raw = attrs["raw_data_"]
+        if _is_sparse(raw):
+            del attrs["raw_data_"]
+            attrs["raw_data_indptr"] = np.asarray(raw.indptr)
+            attrs["raw_data_indices"] = np.asarray(raw.indices)
+            attrs["raw_data_data"] = np.asarray(raw.data)
+            attrs["raw_data_shape"] = np.asarray(raw.shape, dtype=np.int64)
+        return attrs
 
     @property
     def embedding(self) -> np.ndarray:
         return self._model_attributes["embedding_"]
 
     @property
-    def rawData(self) -> np.ndarray:
+    def rawData(self) -> Any:
+        """The training rows: an ndarray, or a scipy CSR matrix for a model
+        fitted on sparse input (reference umap.py:1352-1383)."""
         return self._model_attributes["raw_data_"]
 
     def _out_col_name(self) -> str:
@@ -708,19 +825,27 @@ class UMAPModel(_UMAPParams, Model):
         from ..parallel.context import get_comm
 
         device = get_comm().device
-        Xt = to_device_tensor(np.ascontiguousarray(X, dtype=np.float32), device)
-        n_new = Xt.shape[0]
+        n_new = X.shape[0]
         if n_new == 0:
             return np.zeros((0, self.embedding.shape[1]), dtype=np.float32)
-        raw = to_device_tensor(self.rawData, device)
+        sparse = _is_sparse(self.rawData)
         emb = to_device_tensor(self.embedding, device)
         k = int(float(self.getOrDefault("n_neighbors")))
-        k = min(k, raw.shape[0])
-        metric, p = self._metric()
-        if metric == "euclidean":
-            d, i = knn_topk(Xt, raw, k)
+        k = min(k, self.rawData.shape[0])
+        metric, p = self._metric(sparse)
+        if sparse:
+            # a CSR batch as is, a dense batch converted (knn_topk_metric_sparse
+            # canonicalises either); the model's rows stay CSR
+            d, i = knn_topk_metric_sparse(X, self.rawData, k, metric, p, device=device)
         else:
-            d, i = knn_topk_metric(Xt, raw, k, metric, p)
+            if _is_sparse(X):
+                X = X.toarray()
+            Xt = to_device_tensor(np.ascontiguousarray(X, dtype=np.float32), device)
+            raw = to_device_tensor(self.rawData, device)
+            if metric == "euclidean":
+                d, i = knn_topk(Xt, raw, k)
+            else:
+                d, i = knn_topk_metric(Xt, raw, k, metric, p)
         # device-resident smooth-knn + membership weights (the numpy hop
         # cost seconds at 1M transform rows)
         sigma, rho = _smooth_knn_t(d, float(self.getOrDefault("local_connectivity")))

@@ -9,14 +9,16 @@ Falls back to the chunked torch path for k > 64 or CPU.
 `knn_topk_metric` serves the metrics other than euclidean (UMAP's `metric`):
 dot-product metrics on preprocessed rows through the same GEMM + selection
 path, per-coordinate metrics through the `pairwise_dist` tile kernel +
-`knn_merge_topk_keys`.
+`knn_merge_topk_keys`. `knn_topk_metric_sparse` is its CSR twin: the
+`csr_pairwise` kernel walks only the stored entries of both sides.
 """
 
 from __future__ import annotations
 
 import math
-from typing import Callable, Dict, Tuple
+from typing import Any, Callable, Dict, Tuple
 
+import numpy as np
 import torch
 
 from . import torch_ref
@@ -146,13 +148,22 @@ TILE_OPS: Dict[str, int] = {
 }
 
 
-def resolve_metric(metric: str, p: float = 2.0) -> Tuple[str, float]:
+def resolve_metric(metric: str, p: float = 2.0, sparse: bool = False) -> Tuple[str, float]:
     """(canonical metric, p) of a metric name or alias. minkowski with p = 1
     and p = 2 resolves to manhattan and euclidean. ValueError for jaccard
-    (dense inputs), an unknown name, or a p that is not finite and > 0."""
+    (dense inputs), an unknown name, or a p that is not finite and > 0.
+    With `sparse`, jaccard resolves and the metrics that have no sparse form
+    (chebyshev, correlation) raise ValueError."""
     name = str(metric).lower()
     if name == "jaccard":
+        if sparse:
+            return "jaccard", 2.0
         raise ValueError("Metric 'jaccard' not supported for dense inputs.")
+    if sparse and METRIC_ALIASES.get(name) in ("chebyshev", "correlation"):
+        raise ValueError(
+            f"metric {METRIC_ALIASES[name]!r} is not supported for sparse input "
+            f"(accepted: {', '.join(torch_ref.SPARSE_METRICS)})"
+        )
     if name not in METRIC_ALIASES:
         raise ValueError(
             f"Unknown metric {metric!r}; accepted: {', '.join(sorted(METRIC_ALIASES))}"
@@ -231,3 +242,171 @@ def _tile_select_keys(
         ext.knn_merge_topk_keys(Gv, s, best_d, best_i)
 
     return _chunked_select(Q.shape[0], I.shape[0], k, Q.device, chunk_elems, merge_chunk)
+
+
+# ---------------------------------------------------------------------------
+# sparse (CSR) input: the `csr_pairwise` kernel in place of `pairwise_dist`
+# ---------------------------------------------------------------------------
+
+# metric -> `csr_pairwise` op code
+SPARSE_OPS: Dict[str, int] = {
+    "euclidean": 0, "sqeuclidean": 0, "cosine": 0, "hellinger": 0,
+    "manhattan": 1, "minkowski": 2, "canberra": 3, "hamming": 4, "jaccard": 5,
+}
+# items per `csr_pairwise` call: 4 query rows x chunk f32 accumulators of LDS
+# per block (8192 -> 128 KB, one block per CU; profiles/README.md)
+SPARSE_CHUNK = 8192
+
+
+def canonical_csr(M: Any) -> Any:
+    """scipy CSR, f32, column ids sorted within a row, no stored zeros. The
+    input is not modified."""
+    import scipy.sparse as sp
+
+    if not sp.issparse(M):
+        M = sp.csr_matrix(np.asarray(M, dtype=np.float32))
+    out = M.tocsr().astype(np.float32)  # astype copies
+    out.sum_duplicates()
+    out.eliminate_zeros()
+    out.sort_indices()
+    return out
+
+
+def _sparse_rows(M: Any, metric: str, p: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(values, per-row constant) of a canonical CSR under `metric`, both f32
+    host tensors: values preprocessed as the dense path preprocesses rows
+    (unit rows for cosine, sqrt for hellinger), the constant sum_j f(x_j, 0).
+    The row sums are taken on the host in one fixed order (a device
+    index_add_ is atomic), which the bit-reproducible graph needs."""
+    vals = M.data
+    n = M.shape[0]
+    counts = np.diff(M.indptr)
+    filled = counts > 0
+
+    def row_sum(v: np.ndarray) -> torch.Tensor:
+        out = np.zeros(n, dtype=np.float32)
+        if v.size:  # empty rows own no segment
+            out[filled] = np.add.reduceat(v, M.indptr[:-1][filled])
+        return torch.from_numpy(out)
+
+    zeros = torch.zeros(n, dtype=torch.float32)
+    if metric in ("euclidean", "sqeuclidean"):
+        const = row_sum(vals * vals)
+    elif metric == "cosine":
+        norm = np.sqrt(row_sum(vals * vals).numpy())
+        if bool((norm == 0).any()):
+            raise ValueError("metric='cosine' is undefined for zero-norm rows")
+        vals, const = vals / np.repeat(norm, counts), zeros
+    elif metric == "hellinger":
+        if bool((vals < 0).any()):
+            raise ValueError("metric='hellinger' requires non-negative inputs")
+        vals, const = np.sqrt(vals), zeros
+    elif metric == "manhattan":
+        const = row_sum(np.abs(vals))
+    elif metric == "minkowski":
+        const = row_sum(np.abs(vals) ** np.float32(p))
+    else:  # canberra, hamming, jaccard: nnz
+        const = torch.from_numpy(counts.astype(np.float32))
+    return torch.from_numpy(vals), const
+
+
+def knn_topk_metric_sparse(
+    Q: Any,
+    I: Any,
+    k: int,
+    metric: str = "euclidean",
+    p: float = 2.0,
+    device: Any = None,
+    chunk: int = SPARSE_CHUNK,
+    chunk_elems: int = 1 << 29,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(dists f32 [q,k] ascending, idx int64 [q,k]) of scipy CSR queries
+    against scipy CSR items under `metric`, on `device` (default: the GPU
+    where there is one). Accepted: euclidean/l2, sqeuclidean, cosine,
+    hellinger, manhattan and its aliases, minkowski, canberra, hamming,
+    jaccard; chebyshev and correlation raise ValueError.
+
+    On the GPU each item chunk is turned into CSC in torch and the
+    `csr_pairwise` kernel writes its [q, chunk] key block, which
+    `knn_merge_topk_keys` folds into the running top-k; only stored entries
+    are ever touched. The block never exceeds `chunk_elems` elements (2 GB by
+    default, as on the dense path): queries are taken in tiles of
+    chunk_elems // chunk rows, each against every item chunk. CPU devices
+    and k > 64 take the torch path, which densifies bounded row chunks."""
+    metric, p = resolve_metric(metric, p, sparse=True)
+    if Q.shape[1] != I.shape[1]:
+        raise ValueError(f"queries have {Q.shape[1]} columns, items {I.shape[1]}")
+    same = Q is I
+    I = canonical_csr(I)
+    Q = I if same else canonical_csr(Q)
+    if device is None:
+        device = "cuda" if torch.cuda.is_available() else "cpu"
+    dev = torch.device(device)
+    nq, ni, d = Q.shape[0], I.shape[0], I.shape[1]
+    kernel_path = (
+        dev.type == "cuda"
+        and use_hip(torch.empty(0, device=dev))
+        and k <= min(64, ni)
+        and nq > 0
+    )
+    if not kernel_path:
+        return torch_ref.knn_topk_metric_sparse(Q, I, k, metric, p, dev)
+    if d >= 1 << 31:
+        raise ValueError("sparse kNN supports fewer than 2^31 columns")
+    if not 256 <= chunk <= SPARSE_CHUNK:  # 256: _chunked_select's floor
+        raise ValueError(f"chunk must be in [256, {SPARSE_CHUNK}]")
+    ext = hip_ops()
+    op = SPARSE_OPS[metric]
+
+    i_val, B = _sparse_rows(I, metric, p)
+    q_val, A = (i_val, B) if same else _sparse_rows(Q, metric, p)
+    if metric in ("cosine", "hellinger"):
+        # key = 1 - <q', x'>: A = 1, B = 0 and the query values halved (exact)
+        # so that the kernel's -2 acc is -<q', x'>, as in knn_topk_metric
+        q_val = q_val * 0.5
+        A = torch.ones(nq, dtype=torch.float32)
+    q_ptr = torch.from_numpy(Q.indptr.astype(np.int64)).to(dev)
+    q_col = torch.from_numpy(Q.indices.astype(np.int32)).to(dev)
+    q_val = q_val.contiguous().to(dev)
+    A = A.to(dev)
+    B = B.to(dev)
+    i_ptr = I.indptr.astype(np.int64)  # host: chunk bounds cost no sync
+    i_col = torch.from_numpy(I.indices.astype(np.int64)).to(dev)
+    i_val = i_val.contiguous().to(dev)
+    i_cnt = torch.from_numpy(np.diff(i_ptr)).to(dev)
+    zero = torch.zeros(1, dtype=torch.int64, device=dev)
+
+    def csc_chunk(s, e):
+        a, b = int(i_ptr[s]), int(i_ptr[e])
+        # CSC of item rows s:e: a stable sort by column id keeps the rows of
+        # one column ascending
+        cols, order = torch.sort(i_col[a:b], stable=True)
+        local = torch.repeat_interleave(
+            torch.arange(e - s, device=dev, dtype=torch.int32), i_cnt[s:e], output_size=b - a
+        )
+        colptr = torch.cat([zero, torch.cumsum(torch.bincount(cols, minlength=d), dim=0)])
+        return colptr, local[order].contiguous(), i_val[a:b][order].contiguous()
+
+    def select_tile(qs, qe):
+        # indptr keeps its absolute offsets into q_col / q_val
+        t_ptr, t_A = q_ptr[qs:qe + 1].contiguous(), A[qs:qe].contiguous()
+
+        def merge_chunk(Gv, s, e, best_d, best_i):
+            colptr, c_row, c_val = csc_chunk(s, e)
+            ext.csr_pairwise(
+                t_ptr, q_col, q_val, colptr, c_row, c_val, t_A, B[s:e].contiguous(),
+                op, float(p), Gv,
+            )
+            ext.knn_merge_topk_keys(Gv, s, best_d, best_i)
+
+        return _chunked_select(qe - qs, ni, k, dev, chunk * (qe - qs), merge_chunk)
+
+    # one tile unless nq * chunk passes the budget (65 536 rows at 8192 items);
+    # beyond it each tile rebuilds the chunk CSCs, a sort of nnz per tile
+    qtile = max(4, chunk_elems // chunk)
+    tiles = [select_tile(qs, min(nq, qs + qtile)) for qs in range(0, nq, qtile)]
+    keys = torch.cat([t[0] for t in tiles]) if len(tiles) > 1 else tiles[0][0]
+    idx = torch.cat([t[1] for t in tiles]) if len(tiles) > 1 else tiles[0][1]
+    if metric == "euclidean":
+        return torch.sqrt(torch.clamp(keys, min=0.0)), idx
+    return torch_ref.finish_keys(keys, metric, p, d), idx

@@ -7,7 +7,7 @@ CPU test path stays memory-bounded on large inputs.
 
 from __future__ import annotations
 
-from typing import Optional, Tuple
+from typing import Any, Optional, Tuple
 
 import torch
 
@@ -185,6 +185,8 @@ def finish_keys(keys: torch.Tensor, metric: str, p: float, d: int) -> torch.Tens
         return torch.clamp(keys, min=0.0)
     if metric == "hellinger":
         return torch.sqrt(torch.clamp(keys, min=0.0))
+    if metric == "jaccard":
+        return keys  # the key is the distance
     return keys
 
 
@@ -259,6 +261,82 @@ def knn_topk_metric(
             best_d, best_i = vals, ids
         best_d, order = torch.sort(best_d, dim=1)
         dists[s:e] = finish_keys(best_d, metric, p, d)
+        idx[s:e] = best_i.gather(1, order)
+    return dists, idx
+
+
+# metrics defined for sparse (CSR) input: every one has f(0, 0) = 0 and sums
+# over coordinates, so a pair's distance needs only the stored entries.
+# chebyshev (a max) and correlation (centring fills the row) do not qualify.
+SPARSE_METRICS = (
+    "euclidean", "sqeuclidean", "cosine", "hellinger",
+    "manhattan", "minkowski", "canberra", "hamming", "jaccard",
+)
+
+
+def _jaccard_keys(Q: torch.Tensor, I: torch.Tensor) -> torch.Tensor:
+    """[q, n] jaccard distances of the boolean (nonzero) patterns of dense
+    rows; two empty rows are at distance 0."""
+    Qb = (Q != 0).to(torch.float32)
+    Ib = (I != 0).to(torch.float32)
+    inter = Qb @ Ib.T
+    union = Qb.sum(dim=1)[:, None] + Ib.sum(dim=1)[None, :] - inter
+    return torch.where(union > 0, 1.0 - inter / union.clamp(min=1.0), torch.zeros_like(inter))
+
+
+def knn_topk_metric_sparse(
+    Q: Any,
+    I: Any,
+    k: int,
+    metric: str = "euclidean",
+    p: float = 2.0,
+    device: Any = None,
+    block_elems: int = 1 << 24,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Brute-force kNN of scipy CSR queries against scipy CSR items under a
+    canonical metric of SPARSE_METRICS: (dists f32 [q,k] ascending, idx int64
+    [q,k]) on `device`. Row chunks of both sides are densified, never more
+    than block_elems elements at a time, and go through `_metric_keys`;
+    jaccard is computed from the boolean rows."""
+    if metric not in SPARSE_METRICS:
+        raise ValueError(f"metric {metric!r} is not supported for sparse input")
+    dev = torch.device(device) if device is not None else torch.device("cpu")
+    nq, ni, d = Q.shape[0], I.shape[0], I.shape[1]
+    k = min(k, ni)
+    key_metric = "sqeuclidean" if metric == "euclidean" else metric
+
+    def dense(M, s, e):
+        X = torch.from_numpy(M[s:e].toarray().astype("float32", copy=False)).to(dev)
+        if metric in ("cosine", "hellinger"):
+            X = metric_rows(X, metric)
+        return X
+
+    ichunk = max(k, min(ni, 4096, max(1, block_elems // max(1, d))))
+    qchunk = max(1, min(nq, block_elems // max(1, d, ichunk)))
+    dists = torch.empty((nq, k), dtype=torch.float32, device=dev)
+    idx = torch.empty((nq, k), dtype=torch.int64, device=dev)
+    for s in range(0, nq, qchunk):
+        e = min(nq, s + qchunk)
+        Qd = dense(Q, s, e)
+        best_d = best_i = None
+        for s2 in range(0, ni, ichunk):
+            e2 = min(ni, s2 + ichunk)
+            Id = dense(I, s2, e2)
+            if metric == "jaccard":
+                keys = _jaccard_keys(Qd, Id)
+            else:
+                keys = _metric_keys(Qd, Id, key_metric, p, block_elems)
+            vals, ids = torch.topk(keys, min(k, e2 - s2), dim=1, largest=False)
+            ids = ids + s2
+            if best_d is not None:
+                vals = torch.cat([best_d, vals], dim=1)
+                ids = torch.cat([best_i, ids], dim=1)
+                vals, order = torch.topk(vals, min(k, vals.shape[1]), dim=1, largest=False)
+                ids = ids.gather(1, order)
+            best_d, best_i = vals, ids
+        best_d, order = torch.sort(best_d, dim=1)
+        out = finish_keys(best_d, key_metric, p, d)
+        dists[s:e] = torch.sqrt(out) if metric == "euclidean" else out
         idx[s:e] = best_i.gather(1, order)
     return dists, idx
 

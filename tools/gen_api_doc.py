@@ -62,9 +62,11 @@ Any other DBSCAN metric raises `ValueError` at `transform`.
 | `minkowski` | (Σ\\|x−y\\|ᵖ)^(1/p), `p` from `metric_kwds` (default 2; finite and > 0; 1 and 2 resolve to manhattan and euclidean) | same | raises |
 | `canberra` | Σ\\|x−y\\|/(\\|x\\|+\\|y\\|), 0/0 = 0 | same | raises |
 | `hamming` | (#coordinates with xᵢ≠yᵢ)/d | same | raises |
-| `jaccard` | — | raises `Metric 'jaccard' not supported for dense inputs.` (there is no sparse UMAP input) | — |
+| `jaccard` | 1 − \\|nz(x)∩nz(y)\\|/\\|nz(x)∪nz(y)\\| of the stored-entry patterns, 0 for two empty rows | sparse input only (below); dense input raises `Metric 'jaccard' not supported for dense inputs.` | raises |
 
 Under `build_algo="auto"` the per-coordinate metrics and hellinger build the graph by brute force at any size; the L2-reducible ones switch to nn-descent above 50 000 rows as euclidean does. An unknown name raises and lists the accepted names.
+
+Sparse input. A scipy CSR feature column stays CSR (`enable_sparse_data_optim`: `None` follows the input, `True` requires CSR, `False` densifies as before). The graph is then built by `ops/knn.py::knn_topk_metric_sparse`: per item chunk a CSC is built in torch and the `csr_pairwise` HIP kernel walks only the stored entries of both sides, `knn_merge_topk_keys` keeps the running top-k. Every metric above except `chebyshev`/`linf` and `correlation` is accepted, plus `jaccard`; those two and `build_algo="nn_descent"` raise a `ValueError` naming "sparse input" (`auto` means brute force). `UMAPModel.rawData` is then a `scipy.sparse.csr_matrix`, persisted as its three arrays and shape; `transform` takes a CSR batch as is and converts a dense one.
 
 ## Evaluators
 
