@@ -2455,6 +2455,245 @@ __global__ __launch_bounds__(256) void ivf_scan_topk_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// ivfpq_scan_topk: fused IVF-PQ ADC scan. One 256-thread block per (query,
+// probed list) pair, because the pair's lookup table lives in LDS and is
+// shared by the block's four waves:
+//   1. stage q - C[l] (MODE 0) or q (MODE 1) in LDS and build
+//        MODE 0: LUT[m][c] = sum_j (qres[m*ds+j] - cb[m][c][j])^2
+//        MODE 1: LUT[m][c] = -sum_j q[m*ds+j] * cb[m][c][j]   (+ base -q.C[l])
+//      in the difference form of ivf_scan_topk. Thread t owns code
+//      t % ncodes and walks m from t / ncodes in steps of 256 / ncodes, so
+//      one step of the block reads a contiguous run of the codebooks.
+//   2. each lane takes one list row per trip (a wave 64 consecutive rows,
+//      the block 256), reads its M code bytes — as dwords when the row stride
+//      and base allow (`vec4`; the stride may be padded past M), else as
+//      bytes — and sums LUT[m][code & (ncodes-1)]: the mask keeps every index
+//      inside its LUT row whatever the bytes hold.
+//   3. keys are per lane, so insertion is the candidate-ballot loop of
+//      knn_merge_topk with the same wave-uniform trip count. A lane owns
+//      SLOTS statically indexed slots (slot s*64+lane, live below k_cand,
+//      dead = -inf otherwise); each wave keeps the best k_cand of its quarter
+//      of the rows, waves 1-3 park theirs in LDS (key + i32 offset from the
+//      list start) and wave 0 merges them through the same insert.
+// The LUT gathers of step 2 hit random banks and will conflict; that cost is
+// accepted here and has not been measured.
+// Dynamic LDS: LUT M*ncodes*4 | query d*4 (padded to 16 B) | 3*64*SLOTS*8.
+// Reference: cuVS ivf_pq search (knn.py:1512-1515).
+// ---------------------------------------------------------------------------
+
+constexpr int64_t PQ_LDS_BUDGET = 144 * 1024;
+
+static inline int64_t ivfpq_lds_bytes(int64_t M, int64_t ncodes, int64_t d, int64_t slots) {
+  return M * ncodes * 4 + ((d + 3) / 4) * 16 + 3 * 64 * slots * 8;
+}
+
+// one candidate-ballot insert round: every lane of the wave must call it
+template <int SLOTS>
+__device__ inline void pq_insert(float key, int pos, bool valid, float (&cur_k)[SLOTS],
+                                 int (&cur_p)[SLOTS], float& tau) {
+  unsigned long long m = __ballot(valid && key < tau);
+  while (m) {
+    const int src = __ffsll((unsigned long long)m) - 1;
+    m &= m - 1;
+    const float v = __shfl(key, src, 64);
+    if (v >= tau) continue;  // tau shrank since the ballot
+    const int vp = __shfl(pos, src, 64);
+    float lmax = cur_k[0];
+#pragma unroll
+    for (int s = 1; s < SLOTS; ++s) lmax = fmaxf(lmax, cur_k[s]);
+    // evict the current worst slot
+    const unsigned long long owners = __ballot(lmax == tau);
+    const int owner = __ffsll((unsigned long long)owners) - 1;
+    if ((int)(threadIdx.x & 63) == owner) {
+      bool done = false;
+#pragma unroll
+      for (int s = 0; s < SLOTS; ++s) {
+        if (!done && cur_k[s] == tau) { cur_k[s] = v; cur_p[s] = vp; done = true; }
+      }
+    }
+    lmax = cur_k[0];
+#pragma unroll
+    for (int s = 1; s < SLOTS; ++s) lmax = fmaxf(lmax, cur_k[s]);
+    tau = wave_max_f32(lmax);
+  }
+}
+
+template <int SLOTS, int MODE>
+__global__ __launch_bounds__(256) void ivfpq_scan_topk_kernel(
+    const float* __restrict__ Q,            // [nq, d]
+    const float* __restrict__ C,            // [nlist, d]
+    const float* __restrict__ cb,           // [M, ncodes, ds]
+    const uint8_t* __restrict__ codes,      // [n, stride] rows sorted by list
+    const int64_t* __restrict__ list_off,   // [nlist + 1]
+    const int64_t* __restrict__ pair_q,     // [P]
+    const int64_t* __restrict__ pair_list,  // [P]
+    const int64_t* __restrict__ pair_out,   // [P] output row of each pair
+    int64_t P, int64_t nq, int64_t n, int64_t nlist, int64_t n_out, int d, int M,
+    int ncodes, int ds, int64_t stride, int vec4, int k_cand,
+    float* __restrict__ part_key,           // [n_out, 64*SLOTS]
+    int64_t* __restrict__ part_pos) {       // [n_out, 64*SLOTS] positions into codes
+  extern __shared__ __attribute__((aligned(16))) unsigned char pq_smem[];
+  float* lut = reinterpret_cast<float*>(pq_smem);
+  float* qs = lut + (size_t)M * ncodes;
+  float* mk = qs + (size_t)((d + 3) / 4) * 4;
+  int* mp = reinterpret_cast<int*>(mk + 3 * 64 * SLOTS);
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const int64_t p = blockIdx.x;
+  if (p >= P) return;
+  const int64_t qi = pair_q[p];
+  const int64_t li = pair_list[p];
+  const int64_t oi = pair_out[p];
+  // a malformed work item is dropped, never dereferenced (block-uniform, so
+  // the barriers below are reached by all threads or none)
+  if (qi < 0 || qi >= nq || li < 0 || li >= nlist || oi < 0 || oi >= n_out) return;
+  int64_t lo = list_off[li], hi = list_off[li + 1];
+  lo = lo < 0 ? 0 : (lo > n ? n : lo);
+  hi = hi < 0 ? 0 : (hi > n ? n : hi);
+  // offsets from the list start are kept as i32
+  if (hi - lo > 0x7fffffffLL) hi = lo + 0x7fffffffLL;
+
+  float cur_k[SLOTS];
+  int cur_p[SLOTS];
+#pragma unroll
+  for (int s = 0; s < SLOTS; ++s) {
+    // slots >= k_cand are dead (-inf never owns tau); live slots start empty
+    cur_k[s] = (s * 64 + lane < k_cand) ? INFINITY : -INFINITY;
+    cur_p[s] = -1;
+  }
+
+  if (hi > lo) {  // block-uniform
+    const float* qrow = Q + qi * d;
+    const float* crow = C + li * d;
+    for (int i = tid; i < d; i += 256)
+      qs[i] = MODE == 0 ? qrow[i] - crow[i] : qrow[i];
+    __syncthreads();
+
+    // ---- phase 1: the pair's LUT
+    {
+      const int code = tid & (ncodes - 1);
+      const int mstep = 256 / ncodes;
+      for (int m = tid / ncodes; m < M; m += mstep) {
+        const float* cv = cb + ((size_t)m * ncodes + code) * ds;
+        const float* qv = qs + m * ds;
+        float acc = 0.0f;
+        if ((ds & 3) == 0) {  // cb base is 16 B aligned (checked on the host)
+          for (int j = 0; j < ds; j += 4) {
+            const float4 c4 = *reinterpret_cast<const float4*>(cv + j);
+            const float cj[4] = {c4.x, c4.y, c4.z, c4.w};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              if (MODE == 0) {
+                const float diff = qv[j + e] - cj[e];
+                acc = fmaf(diff, diff, acc);
+              } else {
+                acc = fmaf(qv[j + e], cj[e], acc);
+              }
+            }
+          }
+        } else {
+          for (int j = 0; j < ds; ++j) {
+            if (MODE == 0) {
+              const float diff = qv[j] - cv[j];
+              acc = fmaf(diff, diff, acc);
+            } else {
+              acc = fmaf(qv[j], cv[j], acc);
+            }
+          }
+        }
+        lut[m * ncodes + code] = MODE == 0 ? acc : -acc;
+      }
+    }
+    // MODE 1: the pair's base -q.C[l], computed by every wave for itself
+    float base = 0.0f;
+    if (MODE == 1) {
+      for (int i = lane; i < d; i += 64) base = fmaf(qs[i], crow[i], base);
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) base += __shfl_xor(base, off, 64);
+      base = -base;
+    }
+    __syncthreads();
+
+    // ---- phase 2 + 3: scan the list, keep the wave's best k_cand
+    float tau = INFINITY;
+    const int cmask = ncodes - 1;
+    const int nword = M >> 2, ntail = M & 3;
+    const int64_t len = hi - lo;
+    // UNIFORM trip count (see knn_merge_topk_kernel): lanes past the end of
+    // the list still take part in every ballot and shuffle
+    const int64_t n_iter = (len + 255) / 256;
+    for (int64_t it = 0; it < n_iter; ++it) {
+      const int64_t off = it * 256 + wave * 64 + lane;
+      const bool valid = off < len;
+      float key = INFINITY;
+      if (valid) {
+        const uint8_t* row = codes + (lo + off) * stride;
+        float a0 = base, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
+        if (vec4) {
+          const uint32_t* row4 = reinterpret_cast<const uint32_t*>(row);
+          const float* lrow = lut;
+#pragma unroll 4
+          for (int w = 0; w < nword; ++w) {
+            const uint32_t v = row4[w];
+            a0 += lrow[(int)(v & 0xff) & cmask];
+            a1 += lrow[ncodes + ((int)((v >> 8) & 0xff) & cmask)];
+            a2 += lrow[2 * ncodes + ((int)((v >> 16) & 0xff) & cmask)];
+            a3 += lrow[3 * ncodes + ((int)(v >> 24) & cmask)];
+            lrow += 4 * ncodes;
+          }
+          if (ntail) {  // stride % 4 == 0 and stride >= M: the word is in the row
+            const uint32_t v = row4[nword];
+            a0 += lrow[(int)(v & 0xff) & cmask];
+            if (ntail > 1) a1 += lrow[ncodes + ((int)((v >> 8) & 0xff) & cmask)];
+            if (ntail > 2) a2 += lrow[2 * ncodes + ((int)((v >> 16) & 0xff) & cmask)];
+          }
+        } else {
+          int m = 0;
+          for (; m + 3 < M; m += 4) {
+            a0 += lut[m * ncodes + ((int)row[m] & cmask)];
+            a1 += lut[(m + 1) * ncodes + ((int)row[m + 1] & cmask)];
+            a2 += lut[(m + 2) * ncodes + ((int)row[m + 2] & cmask)];
+            a3 += lut[(m + 3) * ncodes + ((int)row[m + 3] & cmask)];
+          }
+          for (; m < M; ++m) a0 += lut[m * ncodes + ((int)row[m] & cmask)];
+        }
+        key = (a0 + a1) + (a2 + a3);
+      }
+      pq_insert<SLOTS>(key, (int)off, valid, cur_k, cur_p, tau);
+    }
+
+    // ---- merge: waves 1-3 park their slots, wave 0 inserts them
+    if (wave > 0) {
+#pragma unroll
+      for (int s = 0; s < SLOTS; ++s) {
+        mk[(wave - 1) * 64 * SLOTS + s * 64 + lane] = cur_k[s];
+        mp[(wave - 1) * 64 * SLOTS + s * 64 + lane] = cur_p[s];
+      }
+    }
+    __syncthreads();
+    if (wave == 0) {
+      for (int i = 0; i < 3 * SLOTS; ++i) {
+        const float key = mk[i * 64 + lane];
+        const int pos = mp[i * 64 + lane];
+        // dead and empty slots carry position -1
+        pq_insert<SLOTS>(key, pos, pos >= 0, cur_k, cur_p, tau);
+      }
+    }
+  }
+
+  if (wave == 0) {
+#pragma unroll
+    for (int s = 0; s < SLOTS; ++s) {
+      part_key[oi * (64 * SLOTS) + s * 64 + lane] = cur_k[s];
+      part_pos[oi * (64 * SLOTS) + s * 64 + lane] =
+          cur_p[s] >= 0 ? lo + (int64_t)cur_p[s] : (int64_t)-1;
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // CSR GLM kernels (the reference's LogisticRegressionMG sparse path,
 // classification.py:960-966, runs cuML SpMM; torch/rocSPARSE here spent its
 // time in f64 index_add column stats, a 400M-pair radix-sort transpose and
@@ -3426,6 +3665,91 @@ std::vector<torch::Tensor> ivf_scan_topk(torch::Tensor Q, torch::Tensor Xs,
   return {part_key, part_pos};
 }
 
+template <int SLOTS>
+static void ivfpq_scan_topk_launch(int64_t mode, unsigned grid, size_t lds, const float* Q,
+                                   const float* C, const float* cb, const uint8_t* codes,
+                                   const int64_t* list_off, const int64_t* pair_q,
+                                   const int64_t* pair_list, const int64_t* pair_out,
+                                   int64_t P, int64_t nq, int64_t n, int64_t nlist,
+                                   int64_t n_out, int d, int M, int ncodes, int ds,
+                                   int64_t stride, int vec4, int k_cand, float* part_key,
+                                   int64_t* part_pos) {
+  if (mode == 0)
+    hipLaunchKernelGGL((ivfpq_scan_topk_kernel<SLOTS, 0>), dim3(grid), dim3(256), lds,
+                       cur_stream(), Q, C, cb, codes, list_off, pair_q, pair_list,
+                       pair_out, P, nq, n, nlist, n_out, d, M, ncodes, ds, stride, vec4,
+                       k_cand, part_key, part_pos);
+  else
+    hipLaunchKernelGGL((ivfpq_scan_topk_kernel<SLOTS, 1>), dim3(grid), dim3(256), lds,
+                       cur_stream(), Q, C, cb, codes, list_off, pair_q, pair_list,
+                       pair_out, P, nq, n, nlist, n_out, d, M, ncodes, ds, stride, vec4,
+                       k_cand, part_key, part_pos);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+}
+
+// (part_key [n_out, 64*SLOTS], part_pos [n_out, 64*SLOTS]) with SLOTS = 1, 2
+// or 4 for k_cand <= 64, 128, 256. codes_s is [n, stride] with stride >= M:
+// columns past M are padding and are never used as codes.
+std::vector<torch::Tensor> ivfpq_scan_topk(torch::Tensor Q, torch::Tensor C,
+                                           torch::Tensor codebooks, torch::Tensor codes_s,
+                                           torch::Tensor list_off, torch::Tensor pair_q,
+                                           torch::Tensor pair_list, torch::Tensor pair_out,
+                                           int64_t n_out, int64_t k_cand, int64_t mode) {
+  for (const torch::Tensor* t : {&Q, &C, &codebooks})
+    TORCH_CHECK(t->is_cuda() && t->dtype() == torch::kFloat32 && t->is_contiguous(),
+                "ivfpq_scan_topk: Q, C and codebooks must be contiguous f32 device tensors");
+  TORCH_CHECK(codes_s.is_cuda() && codes_s.dtype() == torch::kUInt8 &&
+                  codes_s.is_contiguous() && codes_s.dim() == 2,
+              "ivfpq_scan_topk: codes must be a contiguous [n, M] u8 device tensor");
+  TORCH_CHECK(Q.dim() == 2 && C.dim() == 2 && codebooks.dim() == 3);
+  for (const torch::Tensor* t : {&list_off, &pair_q, &pair_list, &pair_out})
+    TORCH_CHECK(t->is_cuda() && t->dtype() == torch::kInt64 && t->is_contiguous() &&
+                t->dim() == 1);
+  const int64_t P = pair_q.size(0);
+  TORCH_CHECK(pair_list.size(0) == P && pair_out.size(0) == P,
+              "ivfpq_scan_topk: pair arrays differ in length");
+  TORCH_CHECK(list_off.size(0) >= 1);
+  const int64_t nq = Q.size(0), d = Q.size(1), nlist = list_off.size(0) - 1;
+  const int64_t M = codebooks.size(0), ncodes = codebooks.size(1), ds = codebooks.size(2);
+  const int64_t n = codes_s.size(0), stride = codes_s.size(1);
+  TORCH_CHECK(d >= 1 && M >= 1 && ds >= 1 && d == M * ds,
+              "ivfpq_scan_topk: d must equal M * ds");
+  TORCH_CHECK(C.size(0) == nlist && C.size(1) == d,
+              "ivfpq_scan_topk: C must be [nlist, d]");
+  TORCH_CHECK(stride >= M, "ivfpq_scan_topk: code rows are shorter than M");
+  TORCH_CHECK(ncodes >= 1 && ncodes <= 256 && (ncodes & (ncodes - 1)) == 0,
+              "ivfpq_scan_topk: ncodes must be a power of two <= 256");
+  TORCH_CHECK(k_cand >= 1 && k_cand <= 256, "ivfpq_scan_topk supports 1 <= k_cand <= 256");
+  TORCH_CHECK(mode == 0 || mode == 1, "mode must be 0 (L2) or 1 (dot)");
+  TORCH_CHECK(n_out >= 0);
+  const int slots = k_cand <= 64 ? 1 : (k_cand <= 128 ? 2 : 4);
+  const int64_t lds = ivfpq_lds_bytes(M, ncodes, d, slots);
+  TORCH_CHECK(lds <= PQ_LDS_BUDGET, "ivfpq_scan_topk: LUT + query + merge buffer need ",
+              lds, " bytes of LDS, over the ", PQ_LDS_BUDGET, " byte budget");
+  auto part_key = torch::full({n_out, 64 * slots}, INFINITY, Q.options());
+  auto part_pos = torch::full({n_out, 64 * slots}, (int64_t)-1,
+                              Q.options().dtype(torch::kInt64));
+  if (P > 0 && n_out > 0) {
+    TORCH_CHECK(P <= 0x7fffffffLL, "too many (query, list) pairs");
+    const int vec4 = (stride % 4 == 0) && ((uintptr_t)codes_s.data_ptr() % 4 == 0);
+    // the LUT build reads codebook rows as float4 when ds % 4 == 0
+    TORCH_CHECK(ds % 4 != 0 || (uintptr_t)codebooks.data_ptr() % 16 == 0,
+                "ivfpq_scan_topk: codebooks must be 16 B aligned");
+#define IVFPQ_SCAN_ARGS                                                           \
+  mode, (unsigned)P, (size_t)lds, Q.data_ptr<float>(), C.data_ptr<float>(),       \
+      codebooks.data_ptr<float>(), codes_s.data_ptr<uint8_t>(),                   \
+      list_off.data_ptr<int64_t>(), pair_q.data_ptr<int64_t>(),                   \
+      pair_list.data_ptr<int64_t>(), pair_out.data_ptr<int64_t>(), P, nq, n,      \
+      nlist, n_out, (int)d, (int)M, (int)ncodes, (int)ds, stride, vec4,           \
+      (int)k_cand, part_key.data_ptr<float>(), part_pos.data_ptr<int64_t>()
+    if (slots == 1) ivfpq_scan_topk_launch<1>(IVFPQ_SCAN_ARGS);
+    else if (slots == 2) ivfpq_scan_topk_launch<2>(IVFPQ_SCAN_ARGS);
+    else ivfpq_scan_topk_launch<4>(IVFPQ_SCAN_ARGS);
+#undef IVFPQ_SCAN_ARGS
+  }
+  return {part_key, part_pos};
+}
+
 torch::Tensor fil_predict(torch::Tensor X, torch::Tensor feat, torch::Tensor thr,
                           torch::Tensor left, torch::Tensor right, torch::Tensor value,
                           torch::Tensor roots, bool classif) {
@@ -3560,5 +3884,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "[nq, c] distance keys of CSR queries against a CSC item chunk");
   m.def("gather_dists", &gather_dists, "gathered row-vs-candidates squared distances");
   m.def("ivf_scan_topk", &ivf_scan_topk, "fused IVF-Flat probed-list scan + running top-k");
+  m.def("ivfpq_scan_topk", &ivfpq_scan_topk,
+        "fused IVF-PQ ADC scan: in-LDS lookup table + per-pair top-k_cand");
   m.attr("_is_hip") = true;
 }

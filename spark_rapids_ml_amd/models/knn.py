@@ -17,13 +17,16 @@ Spark groupBy aggregation, knn.py:1282-1322). The `metric` param
 (euclidean/l2/sqeuclidean/inner_product/cosine, reference knn.py:1007-1010)
 is carried as a smaller-is-better key through search and merge — see the
 convention table above `_ANN_METRICS`; on the GPU the IVF-Flat probed-list
-scan is the fused `ivf_scan_topk` HIP kernel.
+scan is the fused `ivf_scan_topk` HIP kernel and the IVF-PQ ADC scan the
+fused `ivfpq_scan_topk` kernel. The IVF-PQ index is built once per model and
+parameter set (`_cached_index`) and queried by every later kneighbors call.
 """
 
 from __future__ import annotations
 
 import math
 import os
+from dataclasses import dataclass
 from typing import Any, Dict, Optional, Tuple
 
 import numpy as np
@@ -447,7 +450,27 @@ class ApproximateNearestNeighborsModel(_ANNModelParams, _NNModelBase):
         return self.exactNearestNeighborsJoin(query_df, distCol=distCol)
 
     def _default_nlist(self, n: int) -> int:
-        return max(1, min(1024, int(math.sqrt(max(1, n)))))
+        return _default_nlist(n)
+
+    def _cached_index(self, algo: str, algo_params: Dict[str, Any], metric: str, build):
+        """The index `build()` returns, kept across kneighbors calls under
+        the key (algorithm, sorted algoParams items, metric); the item set is
+        fixed per model, so nothing else can change it. One index is kept: a
+        changed key rebuilds and replaces it. The cache is per rank (index
+        builds run no collectives) and holds the index's device tensors for
+        as long as the model lives. SRML_ANN_CACHE=0 builds on every call."""
+        if os.environ.get("SRML_ANN_CACHE") == "0":
+            return build()
+        key = (
+            algo,
+            tuple(sorted((str(name), repr(v)) for name, v in algo_params.items())),
+            metric,
+        )
+        kept = getattr(self, "_ann_index", None)
+        if kept is None or kept[0] != key:
+            kept = (key, build())
+            self._ann_index = kept
+        return kept[1]
 
     def kneighbors(self, query_df: DataFrame) -> Tuple[DataFrame, DataFrame, DataFrame]:
         algo = self.getOrDefault("algorithm").lower()
@@ -494,21 +517,7 @@ class ApproximateNearestNeighborsModel(_ANNModelParams, _NNModelBase):
 
     # -- IVF-Flat ----------------------------------------------------------
     def _build_coarse(self, Xt: torch.Tensor, nlist: int, iters: int = 10):
-        """Local k-means coarse quantizer (reuses the KMeans assign kernel)."""
-        from ..ops import kmeans_assign_reduce
-
-        n = Xt.shape[0]
-        g = torch.Generator(device="cpu")
-        g.manual_seed(42)
-        sel = torch.randperm(n, generator=g)[:nlist].to(Xt.device)
-        C = Xt[sel].clone()
-        x_sq = (Xt * Xt).sum(dim=1)
-        for _ in range(iters):
-            labels, sums, counts, _ = kmeans_assign_reduce(Xt, C, x_sq)
-            ne = counts > 0
-            C[ne] = (sums[ne] / counts[ne, None]).to(C.dtype)
-        labels, _, _, _ = kmeans_assign_reduce(Xt, C, x_sq)
-        return C, labels.to(torch.int64)
+        return _build_coarse(Xt, nlist, iters)
 
     def _make_ivfflat_search(self, algo_params: Dict[str, Any], metric: str = "euclidean"):
         def search(Qt: torch.Tensor, X: np.ndarray, k: int):
@@ -534,48 +543,55 @@ class ApproximateNearestNeighborsModel(_ANNModelParams, _NNModelBase):
     def _make_ivfpq_search(self, algo_params: Dict[str, Any], metric: str = "euclidean"):
         """IVF-PQ with exact refine (reference ivf_pq + refine,
         knn.py:1512-1515,1643-1651): residual product quantization —
-        per-subspace 256-centroid codebooks trained on coarse residuals,
-        uint8 codes, per-query ADC lookup-table candidate scan over the
-        probed lists, then exact re-rank of refine_ratio*k candidates by
-        the true metric. cosine runs the L2 pipeline on unit-normalised
-        rows; inner_product scans with the dot-product ADC form."""
-        mode = _metric_mode(metric)
+        per-subspace codebooks trained on coarse residuals,
+        uint8 codes (2**n_bits codes per subspace), per-query ADC
+        lookup-table candidate scan over the probed lists, then exact
+        re-rank of refine_ratio*k candidates by the true metric. cosine runs
+        the L2 pipeline on unit-normalised rows; inner_product scans with the
+        dot-product ADC form. The index (`_ivfpq_build`) is kept across calls
+        by `_cached_index`; each call runs `_ivfpq_query` on it."""
+        _ivfpq_n_bits(algo_params)  # a bad n_bits fails before any work
 
         def search(Qt: torch.Tensor, X: np.ndarray, k: int):
             from ..parallel.context import get_comm
 
             device = get_comm().device
-            Xt = to_device_tensor(np.ascontiguousarray(X, dtype=np.float32), device)
+
+            def build():
+                Xt = to_device_tensor(np.ascontiguousarray(X, dtype=np.float32), device)
+                return _ivfpq_build(Xt, algo_params, metric)
+
+            index = self._cached_index("ivfpq", algo_params, metric, build)
             if metric == "cosine":
-                Xt, Qt = _normalize_rows(Xt), _normalize_rows(Qt)
-            n, d = Xt.shape
-            nlist = int(algo_params.get("nlist", self._default_nlist(n)))
+                Qt = _normalize_rows(Qt)
+            nlist = index.boundaries.numel() - 1
             nprobe = int(algo_params.get("nprobe", max(1, nlist // 16)))
             refine = float(algo_params.get("refine_ratio", 2.0))
-            m_sub = int(algo_params.get("M", max(1, d // 4)))
-            while d % m_sub != 0:  # subspace dims must divide d
-                m_sub -= 1
-            k_cand = min(n, max(k, int(k * refine)))
-            C, labels = self._build_coarse(Xt, nlist)
-            resid = Xt - C[labels]
-            codebooks, codes = _pq_encode(resid, m_sub)
-            d_c, i_c = _ivfpq_scan(
-                Qt, C, labels, codebooks, codes, nlist, nprobe, k_cand, mode
-            )
-            # exact refine on candidates (full-precision vectors resident)
-            rows = torch.arange(Qt.shape[0], device=device)[:, None]
-            cand = Xt[i_c.clamp(min=0)]  # [q, k_cand, d]
-            if mode == _MODE_DOT:
-                d_exact = -(Qt[:, None, :] * cand).sum(dim=2)
-            else:
-                d_exact = ((Qt[:, None, :] - cand) ** 2).sum(dim=2)
-            d_exact = torch.where(
-                i_c >= 0, d_exact, torch.full_like(d_exact, float("inf"))
-            )
-            vals, order = torch.topk(d_exact, min(k, k_cand), dim=1, largest=False)
-            return vals, i_c[rows, order]
+            return _ivfpq_query(index, Qt, k, nprobe, refine)
 
         return search
+
+
+def _default_nlist(n: int) -> int:
+    return max(1, min(1024, int(math.sqrt(max(1, n)))))
+
+
+def _build_coarse(Xt: torch.Tensor, nlist: int, iters: int = 10):
+    """Local k-means coarse quantizer (reuses the KMeans assign kernel)."""
+    from ..ops import kmeans_assign_reduce
+
+    n = Xt.shape[0]
+    g = torch.Generator(device="cpu")
+    g.manual_seed(42)
+    sel = torch.randperm(n, generator=g)[:nlist].to(Xt.device)
+    C = Xt[sel].clone()
+    x_sq = (Xt * Xt).sum(dim=1)
+    for _ in range(iters):
+        labels, sums, counts, _ = kmeans_assign_reduce(Xt, C, x_sq)
+        ne = counts > 0
+        C[ne] = (sums[ne] / counts[ne, None]).to(C.dtype)
+    labels, _, _, _ = kmeans_assign_reduce(Xt, C, x_sq)
+    return C, labels.to(torch.int64)
 
 
 def _ivf_search(
@@ -838,7 +854,7 @@ def _graph_beam_search(
 
 def _pq_encode(resid: torch.Tensor, m_sub: int, n_codes: int = 256, iters: int = 8):
     """Train per-subspace codebooks (k-means on a sample) and encode.
-    Returns (codebooks [m, 256, ds], codes uint8 [n, m])."""
+    Returns (codebooks [m, n_codes, ds], codes uint8 [n, m])."""
     n, d = resid.shape
     ds = d // m_sub
     device = resid.device
@@ -949,3 +965,186 @@ def _ivfpq_scan(
             best_d[qsel] = mvals
             best_i[qsel] = cat_i.gather(1, morder)
     return best_d, best_i
+
+
+# -- IVF-PQ index: build once, query many times -------------------------------
+_PQ_LDS_BUDGET = 144 * 1024  # ivfpq_scan_topk: LUT + query + merge buffer
+
+
+@dataclass
+class IvfPqIndex:
+    """What an IVF-PQ search needs of the items, built by `_ivfpq_build`."""
+
+    Xt: torch.Tensor  # [n, d] items (unit rows for cosine), for the refine
+    C: torch.Tensor  # [nlist, d] coarse centres
+    labels: torch.Tensor  # [n] list of each item
+    order: torch.Tensor  # [n] item rows sorted by list
+    boundaries: torch.Tensor  # [nlist + 1] list offsets into `order`
+    codebooks: torch.Tensor  # [M, ncodes, ds]
+    codes: torch.Tensor  # [n, M] u8, item order
+    codes_sorted: torch.Tensor  # [n, M padded to a multiple of 4] u8, list order
+    m_sub: int
+    n_bits: int
+    mode: int
+
+
+def _ivfpq_n_bits(algo_params: Dict[str, Any]) -> int:
+    """algoParams["n_bits"] (reference ivfpq algoParams: nlist, nprobe, M,
+    n_bits): bits per code, an integer 4..8, default 8."""
+    n_bits = algo_params.get("n_bits", 8)
+    ok = isinstance(n_bits, (int, np.integer)) and not isinstance(n_bits, bool)
+    if not ok or not 4 <= int(n_bits) <= 8:
+        raise ValueError(f"n_bits must be an integer from 4 to 8, got {n_bits!r}")
+    return int(n_bits)
+
+
+def _ivfpq_build(Xt: torch.Tensor, algo_params: Dict[str, Any], metric: str) -> IvfPqIndex:
+    """Coarse k-means, residual codebooks of 2**n_bits codes per subspace
+    and the one-byte codes, in item order and in list order."""
+    n_bits = _ivfpq_n_bits(algo_params)
+    if metric == "cosine":
+        Xt = _normalize_rows(Xt)
+    n, d = Xt.shape
+    nlist = int(algo_params.get("nlist", _default_nlist(n)))
+    m_sub = int(algo_params.get("M", max(1, d // 4)))
+    while d % m_sub != 0:  # subspace dims must divide d
+        m_sub -= 1
+    C, labels = _build_coarse(Xt, nlist)
+    resid = Xt - C[labels]
+    codebooks, codes = _pq_encode(resid, m_sub, n_codes=2**n_bits)
+    order = torch.argsort(labels)
+    boundaries = torch.searchsorted(
+        labels[order], torch.arange(nlist + 1, device=Xt.device)
+    )
+    # the kernel reads a row's codes as dwords: pad the list-sorted rows to a
+    # multiple of 4 bytes (the pad columns are never used as codes)
+    codes_sorted = torch.zeros(
+        (n, (m_sub + 3) // 4 * 4), dtype=torch.uint8, device=Xt.device
+    )
+    codes_sorted[:, :m_sub] = codes[order]
+    return IvfPqIndex(
+        Xt=Xt, C=C, labels=labels, order=order, boundaries=boundaries,
+        codebooks=codebooks, codes=codes, codes_sorted=codes_sorted,
+        m_sub=m_sub, n_bits=n_bits, mode=_metric_mode(metric),
+    )
+
+
+def _ivfpq_query(
+    index: IvfPqIndex, Qt: torch.Tensor, k: int, nprobe: int, refine_ratio: float
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """ADC scan for k*refine_ratio candidates, then the exact re-rank.
+    `Qt` is already normalised for cosine. Returns (keys, item rows)."""
+    Xt, mode = index.Xt, index.mode
+    n = Xt.shape[0]
+    k_cand = min(n, max(k, int(k * refine_ratio)))
+    _, i_c = _ivfpq_candidates(index, Qt, nprobe, k_cand)
+    # exact refine on candidates (full-precision vectors resident)
+    rows = torch.arange(Qt.shape[0], device=Qt.device)[:, None]
+    cand = Xt[i_c.clamp(min=0)]  # [q, k_cand, d]
+    if mode == _MODE_DOT:
+        d_exact = -(Qt[:, None, :] * cand).sum(dim=2)
+    else:
+        d_exact = ((Qt[:, None, :] - cand) ** 2).sum(dim=2)
+    d_exact = torch.where(i_c >= 0, d_exact, torch.full_like(d_exact, float("inf")))
+    vals, order = torch.topk(d_exact, min(k, k_cand), dim=1, largest=False)
+    return vals, i_c[rows, order]
+
+
+def _ivfpq_candidates(
+    index: IvfPqIndex, Qt: torch.Tensor, nprobe: int, k_cand: int
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The k_cand best ADC keys per query over its probed lists and their
+    item rows (+inf, -1 for an empty slot): the fused kernel where
+    `_ivfpq_kernel_wanted` says so, the torch scan otherwise."""
+    if _ivfpq_kernel_wanted(index, Qt, k_cand):
+        return _ivfpq_scan_kernel(index, Qt, nprobe, k_cand)
+    nlist = index.boundaries.numel() - 1
+    return _ivfpq_scan(
+        Qt, index.C, index.labels, index.codebooks, index.codes,
+        nlist, nprobe, k_cand, index.mode,
+    )
+
+
+def _pow2_ceil(v: int) -> int:
+    return 1 << max(0, int(v) - 1).bit_length()
+
+
+def _ivfpq_slots(k_cand: int) -> int:
+    """Slots per pair the kernel writes: 64 * SLOTS, SLOTS in {1, 2, 4}."""
+    return 64 if k_cand <= 64 else (128 if k_cand <= 128 else 256)
+
+
+def _ivfpq_kernel_wanted(index: IvfPqIndex, Qt: torch.Tensor, k_cand: int) -> bool:
+    """Route the ADC scan through the `ivfpq_scan_topk` kernel? On the GPU,
+    for f32 inputs, k_cand <= 256 and a lookup table that fits the kernel's
+    LDS budget. SRML_IVFPQ_KERNEL=0 forces the
+    torch scan; =1 asks for the kernel, which it gets wherever it is legal."""
+    from ..ops.dispatch import use_hip
+
+    env = os.environ.get("SRML_IVFPQ_KERNEL")
+    if env == "0" or not (Qt.is_cuda and use_hip(Qt, index.Xt)):
+        return False
+    if Qt.dtype != torch.float32 or index.C.dtype != torch.float32:
+        return False
+    m_sub, n_codes, _ = index.codebooks.shape
+    d = Qt.shape[1]
+    if not 1 <= k_cand <= 256 or n_codes > 256:
+        return False
+    if index.C.shape[0] != index.boundaries.numel() - 1:  # nlist > n
+        return False
+    lds = m_sub * _pow2_ceil(n_codes) * 4 + (d + 3) // 4 * 16 + 3 * _ivfpq_slots(k_cand) * 8
+    if lds > _PQ_LDS_BUDGET:
+        return False
+    return True
+
+
+def _ivfpq_scan_kernel(
+    index: IvfPqIndex, Qt: torch.Tensor, nprobe: int, k_cand: int
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Kernel path of the ADC scan, same results as `_ivfpq_scan`: one block
+    per (query, probed list) pair builds the pair's lookup table in LDS and
+    keeps the list's k_cand best rows in 64*SLOTS slots, then one topk over
+    each query's nprobe*64*SLOTS slots. Pairs are sorted by list, as in
+    `_ivf_scan_kernel`, so neighbouring blocks stream the same code rows."""
+    from ..ops.dispatch import hip_ops
+
+    ext = hip_ops()
+    mode = index.mode
+    nlist = index.boundaries.numel() - 1
+    nprobe = min(nprobe, nlist)
+    probe = _probe_lists(Qt, index.C, nprobe, mode)  # [nq, nprobe]
+    nq = Qt.shape[0]
+    slots = _ivfpq_slots(k_cand)
+    order = index.order
+    list_off = index.boundaries.to(torch.int64).contiguous()
+    codebooks = index.codebooks
+    m_sub, n_codes, ds = codebooks.shape
+    if n_codes & (n_codes - 1):
+        # fewer items than 2**n_bits leave a short codebook: the kernel masks
+        # codes with a power of two, so pad with rows no code refers to
+        pad = codebooks.new_zeros((m_sub, _pow2_ceil(n_codes) - n_codes, ds))
+        codebooks = torch.cat([codebooks, pad], dim=1).contiguous()
+    keys = torch.empty((nq, k_cand), dtype=torch.float32, device=Qt.device)
+    ids = torch.empty((nq, k_cand), dtype=torch.int64, device=Qt.device)
+    # key (f32) + position (i64) slot buffers stay under 512 MB per chunk
+    qchunk = max(1, (512 << 20) // (nprobe * slots * 12))
+    for s in range(0, nq, qchunk):
+        e = min(nq, s + qchunk)
+        flat_list = probe[s:e].reshape(-1)
+        pair_out = torch.argsort(flat_list, stable=True)
+        pair_list = flat_list[pair_out].contiguous()
+        pair_q = torch.div(pair_out, nprobe, rounding_mode="floor")
+        part_key, part_pos = ext.ivfpq_scan_topk(
+            Qt[s:e].contiguous(), index.C.contiguous(), codebooks,
+            index.codes_sorted, list_off, pair_q, pair_list, pair_out,
+            (e - s) * nprobe, k_cand, mode,
+        )
+        part_key = part_key.view(e - s, nprobe * slots)
+        part_pos = part_pos.view(e - s, nprobe * slots)
+        # dead slots (-inf) and never-filled slots -> worst key
+        part_key = part_key.masked_fill(part_pos < 0, float("inf"))
+        vals, loc = torch.topk(part_key, k_cand, dim=1, largest=False)
+        pos = part_pos.gather(1, loc)
+        keys[s:e] = vals
+        ids[s:e] = torch.where(pos >= 0, order[pos.clamp(min=0)], pos)
+    return keys, ids

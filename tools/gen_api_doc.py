@@ -39,6 +39,27 @@ appears when fewer than `k` items are reachable through the probed lists. \
 Exact `NearestNeighbors` has no metric parameter (Euclidean, as in the \
 reference).
 
+`algoParams` of `algorithm="ivfpq"` (the reference's four, plus the refine):
+
+| key | default | meaning |
+|---|---|---|
+| `nlist` | `min(1024, sqrt(n))` | coarse lists |
+| `nprobe` | `max(1, nlist // 16)` | lists scanned per query |
+| `M` | `d // 4`, lowered until it divides `d` | subquantizers |
+| `n_bits` | 8 | bits per code: an integer 4..8, `2**n_bits` codes per subquantizer, one byte per code; anything else raises `ValueError` naming `n_bits` |
+| `refine_ratio` | 2.0 | `k * refine_ratio` ADC candidates (at most `n`) are re-ranked by the true metric |
+
+An ivfpq model builds its index (coarse k-means, codebooks, codes) in the \
+first `kneighbors` call and keeps it: a later call with the same \
+(`algorithm`, `algoParams`, `metric`) only searches and returns bit-identical \
+results for the same queries; a changed key rebuilds. One index is kept per \
+model and per rank. `SRML_ANN_CACHE=0` builds on every call. On the GPU the \
+ADC scan runs the `ivfpq_scan_topk` kernel (f32, `k * refine_ratio <= 256`, \
+`M * 2**n_bits * 4` bytes of lookup table within the 144 KB LDS budget, i.e. \
+`M <= 128` at 8 bits); `SRML_IVFPQ_KERNEL=0` forces the torch scan, which \
+also serves every case the kernel does not take. ivfflat and cagra still \
+build per call.
+
 `DBSCAN(metric=...)` (reference clustering.py:761):
 
 | metric | meaning |
