@@ -2694,6 +2694,251 @@ __global__ __launch_bounds__(256) void ivfpq_scan_topk_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// cagra_search: fused graph beam search, one 256-thread block per query. The
+// whole search state lives in LDS, so a search is one launch instead of a
+// chain of topk / gather / cat / sort launches per hop:
+//   buf     u64 [pow2 >= max(ns, itopk + search_width*deg)]: the sorted list
+//           in buf[0, L) and this iteration's candidates behind it. An entry
+//           is (f32 key bits << 32) | id; non-negative f32 keys order as
+//           unsigned integers, so the u64 order is the (key, id) order. Bit 31
+//           of the low word is the entry's "expanded" flag; ids are < 2^31
+//           and every compare masks the flag out, so it rides along without
+//           entering the order.
+//   hash    i32 [2^hash_bits]: the visited filter, open addressing with
+//           linear probing, -1 = empty.
+//   parents i32 [min(search_width, itopk)], then the query row (f32).
+// Seeding and every iteration share one pipeline: gather ids (seeds, or the
+// parents' graph rows), drop ids outside [0, n) and ids the filter has seen
+// (one atomicCAS per id, so a duplicate inside one iteration is dropped too),
+// key the survivors once with a 16-lane team per candidate row (float4 loads
+// when d % 4 == 0, 4-step butterfly), then one bitonic sort of list +
+// candidates and a trim to itopk. The candidates reach buf in atomic order,
+// which varies from run to run; the sort erases that, and the candidate SET
+// and every count depend only on the inputs.
+// Before an iteration that could take the filter past half full it is cleared
+// and refilled with the list's ids. A node keyed before a reset can be keyed
+// again but sorts behind the list's worst entry, which never gets worse, so
+// resets change stats[1] and stats[2] only.
+// stats = (iterations that expanded a parent, keys computed, filter resets).
+// LDS trade, not measured against alternatives: with hash_bits = 0 the
+// wrapper doubles the filter from its minimum 2*max(itopk+search_width*deg,
+// ns) while the block stays under CG_LDS_TARGET = 32 KiB, i.e. at least five
+// blocks (20 waves) per CU of 160 KiB. The search is a chain of dependent
+// gathers, so resident waves hide its latency; a bigger filter would only
+// save the re-keying after a reset. At the ANN bench shape (d 300, itopk
+// 128, width 16, deg 48) that is 8 KiB buf + 16 KiB filter + 1.3 KiB.
+// Reference: cuVS cagra single-CTA search (knn.py:1521-1524).
+// ---------------------------------------------------------------------------
+
+constexpr int64_t CG_LDS_BUDGET = 144 * 1024;  // hard limit, as ivfpq_scan_topk
+constexpr int64_t CG_LDS_TARGET = 32 * 1024;   // hash_bits = 0 stays under this
+constexpr unsigned long long CG_ORDER_MASK = ~(1ull << 31);
+constexpr unsigned long long CG_EXPANDED = 1ull << 31;
+
+static inline int64_t cg_pow2_ceil(int64_t v) {
+  int64_t p = 1;
+  while (p < v) p <<= 1;
+  return p;
+}
+
+static inline int64_t cagra_lds_bytes(int64_t d, int64_t itopk, int64_t width, int64_t deg,
+                                      int64_t ns, int64_t slots) {
+  const int64_t buf = cg_pow2_ceil(std::max<int64_t>(ns, itopk + width * deg));
+  const int64_t pcap = (std::min<int64_t>(width, itopk) + 3) / 4 * 4;
+  return buf * 8 + slots * 4 + pcap * 4 + (d + 3) / 4 * 16;
+}
+
+// true when `id` was not in the filter yet (and now is). The probe count is
+// bounded by the table size; the load stays <= 1/2, so the bound is never hit.
+__device__ inline bool cg_visit(int* hash, unsigned mask, int shift, int id) {
+  unsigned h = ((unsigned)id * 2654435761u) >> shift;
+  for (unsigned probe = 0; probe <= mask; ++probe) {
+    const int old = atomicCAS(&hash[h & mask], -1, id);
+    if (old == -1) return true;
+    if (old == id) return false;
+    ++h;
+  }
+  return false;
+}
+
+// keys of buf[L, L + ncand) (ids on entry), the pad up to the next power of
+// two, and the sort of buf[0, P2). Returns the new list length. Every thread
+// of the block must call it with the same L and ncand.
+__device__ inline int cg_key_sort_trim(unsigned long long* buf, const float* qs,
+                                       const float* __restrict__ X, int d, bool vec,
+                                       int L, int ncand, int itopk) {
+  const int tid = threadIdx.x;
+  const int team = tid >> 4, tl = tid & 15;
+  for (int c0 = 0; c0 < ncand; c0 += 16) {  // block-uniform trip count
+    const int c = c0 + team;
+    const bool valid = c < ncand;
+    const int id = valid ? (int)(buf[L + c] & 0x7fffffffull) : 0;
+    float acc = 0.0f;
+    if (valid) {
+      if (vec) {
+        const int nvec = d >> 2;
+        const float4* x4 = reinterpret_cast<const float4*>(X + (size_t)id * d);
+        const float4* q4 = reinterpret_cast<const float4*>(qs);
+#pragma unroll 4
+        for (int v = tl; v < nvec; v += 16) {
+          const float4 x = x4[v];
+          const float4 q = q4[v];
+          const float d0 = q.x - x.x, d1 = q.y - x.y, d2 = q.z - x.z, d3 = q.w - x.w;
+          acc = fmaf(d0, d0, acc);
+          acc = fmaf(d1, d1, acc);
+          acc = fmaf(d2, d2, acc);
+          acc = fmaf(d3, d3, acc);
+        }
+      } else {
+        const float* xr = X + (size_t)id * d;
+#pragma unroll 4
+        for (int i = tl; i < d; i += 16) {
+          const float diff = qs[i] - xr[i];
+          acc = fmaf(diff, diff, acc);
+        }
+      }
+    }
+#pragma unroll
+    for (int off = 8; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+    if (valid && tl == 0)
+      buf[L + c] = ((unsigned long long)__float_as_uint(acc) << 32) | (unsigned)id;
+  }
+  const int total = L + ncand;
+  int P2 = 1;
+  while (P2 < total) P2 <<= 1;
+  for (int i = total + tid; i < P2; i += 256) buf[i] = ~0ull;
+  __syncthreads();
+  if (ncand > 0) {  // block-uniform; the list alone is already sorted
+    for (int k2 = 2; k2 <= P2; k2 <<= 1) {
+      for (int j = k2 >> 1; j > 0; j >>= 1) {
+        for (int i = tid; i < (P2 >> 1); i += 256) {
+          const int lo = ((i & ~(j - 1)) << 1) | (i & (j - 1));
+          const int hi = lo | j;
+          const bool asc = (lo & k2) == 0;
+          const unsigned long long a = buf[lo], b = buf[hi];
+          if (((a & CG_ORDER_MASK) > (b & CG_ORDER_MASK)) == asc) {
+            buf[lo] = b;
+            buf[hi] = a;
+          }
+        }
+        __syncthreads();
+      }
+    }
+  }
+  return total < itopk ? total : itopk;
+}
+
+__global__ __launch_bounds__(256) void cagra_search_kernel(
+    const float* __restrict__ Q,    // [nq, d]
+    const float* __restrict__ X,    // [n, d]
+    const int* __restrict__ G,      // [n, deg]
+    const int* __restrict__ seeds,  // [nq, ns]
+    int n, int d, int deg, int ns, int k, int itopk, int width, int max_it,
+    int hash_bits, int vec,
+    float* __restrict__ out_key,    // [nq, k]
+    int* __restrict__ out_id,       // [nq, k]
+    int* __restrict__ stats) {      // [nq, 3]
+  extern __shared__ __attribute__((aligned(16))) unsigned char cg_smem[];
+  __shared__ int s_np, s_ncand;
+  int bufcap = 1;
+  {
+    const int need = ns > itopk + width * deg ? ns : itopk + width * deg;
+    while (bufcap < need) bufcap <<= 1;
+  }
+  const int slots = 1 << hash_bits;
+  const int pcap = ((width < itopk ? width : itopk) + 3) & ~3;
+  unsigned long long* buf = reinterpret_cast<unsigned long long*>(cg_smem);
+  int* hash = reinterpret_cast<int*>(buf + bufcap);
+  int* parents = hash + slots;
+  float* qs = reinterpret_cast<float*>(parents + pcap);
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const int64_t qi = blockIdx.x;
+  const unsigned hmask = (unsigned)slots - 1u;
+  const int hshift = 32 - hash_bits;
+  const int half = slots >> 1;
+
+  // ---- seeding
+  for (int i = tid; i < d; i += 256) qs[i] = Q[qi * d + i];
+  for (int i = tid; i < slots; i += 256) hash[i] = -1;
+  if (tid == 0) s_ncand = 0;
+  __syncthreads();
+  for (int t = tid; t < ns; t += 256) {
+    const int id = seeds[qi * ns + t];
+    if (id >= 0 && id < n && cg_visit(hash, hmask, hshift, id))
+      buf[atomicAdd(&s_ncand, 1)] = (unsigned)id;
+  }
+  __syncthreads();
+  int ncand = s_ncand;
+  int L = cg_key_sort_trim(buf, qs, X, d, vec != 0, 0, ncand, itopk);
+  int hcount = ncand, evals = ncand, iters = 0, resets = 0;
+
+  for (int it = 0; it < max_it; ++it) {
+    // ---- filter reset (every quantity here is block-uniform)
+    const int after = hcount + width * deg < n ? hcount + width * deg : n;
+    if (after > half) {
+      for (int i = tid; i < slots; i += 256) hash[i] = -1;
+      __syncthreads();
+      for (int i = tid; i < L; i += 256)
+        cg_visit(hash, hmask, hshift, (int)(buf[i] & 0x7fffffffull));
+      hcount = L;
+      ++resets;
+      // the parent pick below rewrites buf entries these inserts read
+      __syncthreads();
+    }
+    // ---- 1. parents: the first `width` unexpanded entries in list order
+    if (wave == 0) {
+      int taken = 0;
+      for (int base = 0; base < L && taken < width; base += 64) {
+        const int i = base + lane;
+        const bool un = i < L && !(buf[i] & CG_EXPANDED);
+        const unsigned long long m = __ballot(un);
+        const int r = taken + __popcll(m & ((1ull << lane) - 1ull));
+        if (un && r < width) {
+          parents[r] = (int)(buf[i] & 0x7fffffffull);
+          buf[i] |= CG_EXPANDED;
+        }
+        taken += __popcll(m);
+      }
+      if (lane == 0) {
+        s_np = taken < width ? taken : width;
+        s_ncand = 0;
+      }
+    }
+    __syncthreads();
+    const int np = s_np;
+    if (np == 0) break;  // nothing left to expand
+    ++iters;
+    // ---- 2. candidates: the parents' valid, unvisited graph entries
+    for (int t = tid; t < np * deg; t += 256) {
+      const int p = parents[t / deg];
+      const int id = G[(size_t)p * deg + (t % deg)];
+      if (id >= 0 && id < n && cg_visit(hash, hmask, hshift, id))
+        buf[L + atomicAdd(&s_ncand, 1)] = (unsigned)id;
+    }
+    __syncthreads();
+    ncand = s_ncand;
+    hcount += ncand;
+    evals += ncand;
+    // ---- 3. key, merge, trim
+    L = cg_key_sort_trim(buf, qs, X, d, vec != 0, L, ncand, itopk);
+  }
+
+  for (int i = tid; i < k; i += 256) {
+    const unsigned long long e = buf[i < L ? i : 0];
+    out_key[qi * k + i] = i < L ? __uint_as_float((unsigned)(e >> 32)) : INFINITY;
+    out_id[qi * k + i] = i < L ? (int)(e & 0x7fffffffull) : -1;
+  }
+  if (tid == 0) {
+    stats[qi * 3 + 0] = iters;
+    stats[qi * 3 + 1] = evals;
+    stats[qi * 3 + 2] = resets;
+  }
+}
+
+// ---------------------------------------------------------------------------
 // CSR GLM kernels (the reference's LogisticRegressionMG sparse path,
 // classification.py:960-966, runs cuML SpMM; torch/rocSPARSE here spent its
 // time in f64 index_add column stats, a 400M-pair radix-sort transpose and
@@ -3750,6 +3995,78 @@ std::vector<torch::Tensor> ivfpq_scan_topk(torch::Tensor Q, torch::Tensor C,
   return {part_key, part_pos};
 }
 
+// (keys [nq, k] f32, ids [nq, k] i32, stats [nq, 3] i32) of the graph search
+// specified above cagra_search_kernel. hash_bits = 0 sizes the visited filter
+// here: at least 2*max(itopk + search_width*deg, ns) slots, doubled while the
+// block stays under CG_LDS_TARGET and the table under what 2n ids need.
+std::vector<torch::Tensor> cagra_search(torch::Tensor Q, torch::Tensor X, torch::Tensor G,
+                                        torch::Tensor seeds, int64_t k, int64_t itopk,
+                                        int64_t search_width, int64_t max_iterations,
+                                        int64_t hash_bits) {
+  for (const torch::Tensor* t : {&Q, &X})
+    TORCH_CHECK(t->is_cuda() && t->dtype() == torch::kFloat32 && t->is_contiguous() &&
+                    t->dim() == 2,
+                "cagra_search: Q and X must be contiguous 2-d f32 device tensors");
+  for (const torch::Tensor* t : {&G, &seeds})
+    TORCH_CHECK(t->is_cuda() && t->dtype() == torch::kInt32 && t->is_contiguous() &&
+                    t->dim() == 2,
+                "cagra_search: G and seeds must be contiguous 2-d i32 device tensors");
+  TORCH_CHECK(X.device() == Q.device() && G.device() == Q.device() &&
+                  seeds.device() == Q.device(),
+              "cagra_search: all tensors must be on one device");
+  const int64_t nq = Q.size(0), d = Q.size(1), n = X.size(0);
+  const int64_t deg = G.size(1), ns = seeds.size(1);
+  TORCH_CHECK(X.size(1) == d, "cagra_search: Q and X differ in width");
+  TORCH_CHECK(d >= 1 && d <= 2048, "cagra_search supports 1 <= d <= 2048");
+  TORCH_CHECK(n >= 1 && n < (1LL << 31), "cagra_search supports 1 <= n < 2**31");
+  TORCH_CHECK(G.size(0) == n, "cagra_search: G must have one row per item");
+  TORCH_CHECK(deg >= 1 && deg <= 128, "cagra_search supports 1 <= deg <= 128");
+  TORCH_CHECK(seeds.size(0) == nq, "cagra_search: seeds and Q differ in row count");
+  // seeds share the candidate buffer and the filter with an iteration's
+  // candidates, so they get the same cap as search_width * deg
+  TORCH_CHECK(ns >= 1 && ns <= 2048, "cagra_search supports 1 <= seeds per query <= 2048");
+  TORCH_CHECK(k >= 1 && k <= itopk && itopk <= 512,
+              "cagra_search supports 1 <= k <= itopk <= 512");
+  TORCH_CHECK(search_width >= 1 && search_width * deg <= 2048,
+              "cagra_search supports search_width >= 1 with search_width * deg <= 2048");
+  TORCH_CHECK(max_iterations >= 1, "cagra_search: max_iterations must be >= 1");
+  const int64_t min_slots = cg_pow2_ceil(2 * std::max(itopk + search_width * deg, ns));
+  int64_t slots;
+  if (hash_bits == 0) {
+    const int64_t cap = std::max(min_slots, cg_pow2_ceil(2 * n));
+    slots = min_slots;
+    while (slots * 2 <= cap &&
+           cagra_lds_bytes(d, itopk, search_width, deg, ns, slots * 2) <= CG_LDS_TARGET)
+      slots *= 2;
+  } else {
+    TORCH_CHECK(hash_bits >= 1 && hash_bits <= 24 && (1LL << hash_bits) >= min_slots,
+                "cagra_search: hash_bits must be 0 or give at least ", min_slots,
+                " slots (2 * max(itopk + search_width * deg, seeds per query))");
+    slots = 1LL << hash_bits;
+  }
+  int bits = 0;
+  while ((1LL << bits) < slots) ++bits;
+  const int64_t lds = cagra_lds_bytes(d, itopk, search_width, deg, ns, slots);
+  TORCH_CHECK(lds <= CG_LDS_BUDGET, "cagra_search: list + candidates + visited filter + query need ",
+              lds, " bytes of LDS, over the ", CG_LDS_BUDGET, " byte budget");
+  auto keys = torch::empty({nq, k}, Q.options());
+  auto ids = torch::empty({nq, k}, Q.options().dtype(torch::kInt32));
+  auto stats = torch::empty({nq, 3}, Q.options().dtype(torch::kInt32));
+  if (nq > 0) {
+    TORCH_CHECK(nq <= 0x7fffffffLL, "too many queries");
+    const int vec = (d % 4 == 0) && ((uintptr_t)X.data_ptr() % 16 == 0);
+    const int max_it = (int)std::min<int64_t>(max_iterations, 0x7fffffffLL);
+    hipLaunchKernelGGL(cagra_search_kernel, dim3((unsigned)nq), dim3(256), (size_t)lds,
+                       cur_stream(), Q.data_ptr<float>(), X.data_ptr<float>(),
+                       G.data_ptr<int32_t>(), seeds.data_ptr<int32_t>(), (int)n, (int)d,
+                       (int)deg, (int)ns, (int)k, (int)itopk, (int)search_width, max_it,
+                       bits, vec, keys.data_ptr<float>(), ids.data_ptr<int32_t>(),
+                       stats.data_ptr<int32_t>());
+    C10_HIP_KERNEL_LAUNCH_CHECK();
+  }
+  return {keys, ids, stats};
+}
+
 torch::Tensor fil_predict(torch::Tensor X, torch::Tensor feat, torch::Tensor thr,
                           torch::Tensor left, torch::Tensor right, torch::Tensor value,
                           torch::Tensor roots, bool classif) {
@@ -3886,5 +4203,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ivf_scan_topk", &ivf_scan_topk, "fused IVF-Flat probed-list scan + running top-k");
   m.def("ivfpq_scan_topk", &ivfpq_scan_topk,
         "fused IVF-PQ ADC scan: in-LDS lookup table + per-pair top-k_cand");
+  m.def("cagra_search", &cagra_search,
+        "fused graph beam search: in-LDS itopk list, visited filter and merge per query",
+        py::arg("Q"), py::arg("X"), py::arg("G"), py::arg("seeds"), py::arg("k"),
+        py::arg("itopk"), py::arg("search_width"), py::arg("max_iterations"),
+        py::arg("hash_bits") = 0);
   m.attr("_is_hip") = true;
 }

@@ -18,8 +18,10 @@ Spark groupBy aggregation, knn.py:1282-1322). The `metric` param
 is carried as a smaller-is-better key through search and merge — see the
 convention table above `_ANN_METRICS`; on the GPU the IVF-Flat probed-list
 scan is the fused `ivf_scan_topk` HIP kernel and the IVF-PQ ADC scan the
-fused `ivfpq_scan_topk` kernel. The IVF-PQ index is built once per model and
-parameter set (`_cached_index`) and queried by every later kneighbors call.
+fused `ivfpq_scan_topk` kernel, and the cagra graph search the fused
+`cagra_search` kernel. Every ANN index (IVF-Flat coarse lists, IVF-PQ, the
+cagra graph) is built once per model and build-parameter set (`_cached_index`)
+and queried by every later kneighbors call.
 """
 
 from __future__ import annotations
@@ -368,7 +370,12 @@ def _key_to_dist(key: np.ndarray, metric: str) -> np.ndarray:
 
 class _ANNParams(_NNParams):
     algorithm = Param(
-        "ann", "algorithm", "ivfflat|ivfpq (cagra: reference knn.py:1521).", TypeConverters.toString
+        "ann",
+        "algorithm",
+        "ivfflat|ivfpq|cagra (reference knn.py:1485-1524). cagra algoParams: "
+        "graph_degree, nn_descent_niter (build); itopk_size, search_width, "
+        "max_iterations (search).",
+        TypeConverters.toString,
     )
     algoParams = Param(
         "ann", "algoParams", "algorithm tuning dict.", DictTypeConverters._toDict
@@ -379,8 +386,9 @@ class _ANNParams(_NNParams):
         "metric",
         "distance metric: euclidean|l2|sqeuclidean|inner_product|cosine "
         "(reference knn.py:1007-1010). ivfflat and ivfpq support all five; "
-        "cagra supports euclidean|l2|sqeuclidean. inner_product reports the "
-        "raw dot products, largest first; cosine reports 1 - cos.",
+        "cagra supports euclidean|l2|sqeuclidean and raises for the other "
+        "two. inner_product reports the raw dot products, largest first; "
+        "cosine reports 1 - cos.",
         TypeConverters.toString,
     )
 
@@ -487,7 +495,7 @@ class ApproximateNearestNeighborsModel(_ANNModelParams, _NNModelBase):
                 raise ValueError(
                     f"cagra supports euclidean/l2/sqeuclidean, not {metric!r}"
                 )
-            search = self._make_cagra_search(algo_params)
+            search = self._make_cagra_search(algo_params, metric)
         else:
             raise ValueError(f"unsupported ANN algorithm {algo!r}")
         return self._kneighbors_impl(
@@ -495,23 +503,31 @@ class ApproximateNearestNeighborsModel(_ANNModelParams, _NNModelBase):
         )
 
     # -- CAGRA-equivalent graph ANN ---------------------------------------
-    def _make_cagra_search(self, algo_params: Dict[str, Any]):
+    def _make_cagra_search(self, algo_params: Dict[str, Any], metric: str = "euclidean"):
         """Graph ANN (reference cuVS cagra, knn.py:1521-1524): nn-descent
-        graph build + fixed-hop beam search with itopk_size candidates."""
+        graph build, then a beam search that keeps itopk_size candidates and
+        expands search_width of them per iteration. The graph
+        (`_cagra_build`) is kept across calls by `_cached_index` under its
+        build parameters alone, so the search parameters can change freely;
+        each call runs `_cagra_query` on it."""
+        _cagra_search_params(algo_params, self.getK())  # fails before any work
 
         def search(Qt: torch.Tensor, X: np.ndarray, k: int):
             from ..parallel.context import get_comm
 
             device = get_comm().device
-            Xt = to_device_tensor(np.ascontiguousarray(X, dtype=np.float32), device)
-            degree = int(algo_params.get("graph_degree", 32))
-            build_iters = int(algo_params.get("nn_descent_niter", 3))
-            itopk = int(algo_params.get("itopk_size", max(64, 2 * k)))
-            hops = int(algo_params.get("max_iterations", 8))
-            G = _nn_descent(Xt, degree, build_iters)
-            # cagra's "optimize": augment the search graph with reverse edges
-            G_search = torch.cat([G, _reverse_edges(G, degree // 2)], dim=1)
-            return _graph_beam_search(Qt, Xt, G_search, k, itopk, hops)
+
+            def build():
+                Xt = to_device_tensor(np.ascontiguousarray(X, dtype=np.float32), device)
+                return _cagra_build(Xt, algo_params)
+
+            build_params = {
+                "graph_degree": int(algo_params.get("graph_degree", 32)),
+                "nn_descent_niter": int(algo_params.get("nn_descent_niter", 3)),
+            }
+            index = self._cached_index("cagra", build_params, metric, build)
+            itopk, width, max_it = _cagra_search_params(algo_params, k)
+            return _cagra_query(index, Qt, k, itopk, width, max_it)
 
         return search
 
@@ -524,13 +540,19 @@ class ApproximateNearestNeighborsModel(_ANNModelParams, _NNModelBase):
             from ..parallel.context import get_comm
 
             device = get_comm().device
-            Xt = to_device_tensor(np.ascontiguousarray(X, dtype=np.float32), device)
-            if metric == "cosine":
-                Xt, Qt = _normalize_rows(Xt), _normalize_rows(Qt)
-            n = Xt.shape[0]
-            nlist = int(algo_params.get("nlist", self._default_nlist(n)))
+            nlist = int(algo_params.get("nlist", self._default_nlist(X.shape[0])))
             nprobe = int(algo_params.get("nprobe", max(1, nlist // 16)))
-            C, labels = self._build_coarse(Xt, nlist)
+
+            def build():
+                Xt = to_device_tensor(np.ascontiguousarray(X, dtype=np.float32), device)
+                if metric == "cosine":
+                    Xt = _normalize_rows(Xt)
+                return (Xt,) + tuple(self._build_coarse(Xt, nlist))
+
+            # nprobe is a search parameter: only nlist shapes the index
+            Xt, C, labels = self._cached_index("ivfflat", {"nlist": nlist}, metric, build)
+            if metric == "cosine":
+                Qt = _normalize_rows(Qt)
             mode = _metric_mode(metric)
             return _ivf_search(
                 Qt, Xt, C, labels, nlist, nprobe, k, mode,
@@ -824,9 +846,16 @@ def _nn_descent(X: torch.Tensor, degree: int, n_iter: int) -> torch.Tensor:
 
 
 def _graph_beam_search(
-    Qt: torch.Tensor, Xt: torch.Tensor, G: torch.Tensor, k: int, itopk: int, hops: int
+    Qt: torch.Tensor,
+    Xt: torch.Tensor,
+    G: torch.Tensor,
+    k: int,
+    itopk: int,
+    hops: int,
+    expand: Optional[int] = None,
 ) -> Tuple[torch.Tensor, torch.Tensor]:
-    """Fixed-hop beam search over the kNN graph, vectorized over queries."""
+    """Fixed-hop beam search over the kNN graph, vectorized over queries.
+    `expand` nodes are expanded per hop (default max(4, itopk // 8))."""
     nq = Qt.shape[0]
     n = Xt.shape[0]
     device = Qt.device
@@ -839,7 +868,8 @@ def _graph_beam_search(
         return _gather_dists(Qt, Xt, cand)
 
     bd = qdists(beam)
-    expand = max(4, itopk // 8)  # nodes expanded per hop
+    if expand is None:
+        expand = max(4, itopk // 8)  # nodes expanded per hop
     for _ in range(hops):
         top = beam.gather(1, bd.topk(min(expand, itopk), dim=1, largest=False).indices)
         cand = G[top].reshape(nq, -1)
@@ -850,6 +880,127 @@ def _graph_beam_search(
 
     ids2, vals2 = _dedup_topk(beam, bd, min(k, bd.shape[1]))
     return vals2, ids2  # squared-L2 keys
+
+
+# -- CAGRA index: build once, query many times --------------------------------
+_CAGRA_LDS_BUDGET = 144 * 1024  # cagra_search: list + candidates + filter + query
+# The measured default (RESULTS.md, "CAGRA"): the kernel is the GPU search.
+_CAGRA_KERNEL_DEFAULT = True
+
+
+@dataclass
+class CagraIndex:
+    """What a graph search needs of the items, built by `_cagra_build`."""
+
+    Xt: torch.Tensor  # [n, d] items
+    G: torch.Tensor  # [n, deg] i32 search graph: forward edges, then the
+    # capped reverse edges (filler = the node itself)
+    G64: Optional[torch.Tensor] = None  # i64 copy, made when the torch search first runs
+    seeds: Optional[torch.Tensor] = None  # [nq, itopk] i32 seeds of the last kernel search
+
+
+def _cagra_build(Xt: torch.Tensor, algo_params: Dict[str, Any]) -> CagraIndex:
+    """nn-descent graph of `graph_degree` forward edges, augmented with
+    graph_degree // 2 reverse edges per node (cagra's "optimize" step)."""
+    degree = int(algo_params.get("graph_degree", 32))
+    build_iters = int(algo_params.get("nn_descent_niter", 3))
+    G = _nn_descent(Xt, degree, build_iters)
+    G_search = torch.cat([G, _reverse_edges(G, degree // 2)], dim=1)
+    return CagraIndex(Xt=Xt, G=G_search.to(torch.int32).contiguous())
+
+
+def _cagra_search_params(algo_params: Dict[str, Any], k: int) -> Tuple[int, int, int]:
+    """(itopk_size, search_width, max_iterations) of a search for k.
+    itopk_size defaults to max(64, 2k) and is rounded up to a multiple of 32,
+    as cuVS does; below k it is an error (reference knn.py:1350-1359).
+    search_width defaults to max(4, itopk_size // 8), not cuVS's 1: at width 1
+    ten iterations reach too few nodes (docs/parity.md). max_iterations absent
+    or 0 means ceil(itopk_size / search_width) + 10; the search stops by
+    itself once every kept entry has been expanded."""
+    itopk = int(algo_params.get("itopk_size", max(64, 2 * k)))
+    itopk = max(32, math.ceil(itopk / 32) * 32)
+    if itopk < k:
+        raise ValueError(
+            "cagra increases itopk_size to be closest multiple of 32 and expects "
+            f"the value, i.e. {itopk}, to be larger than or equal to k, i.e. {k})."
+        )
+    width = int(algo_params.get("search_width", max(4, itopk // 8)))
+    if width < 1:
+        raise ValueError(f"search_width must be >= 1, got {width}")
+    max_it = int(algo_params.get("max_iterations", 0) or 0)
+    if max_it <= 0:
+        max_it = math.ceil(itopk / width) + 10
+    return itopk, width, max_it
+
+
+def _cagra_kernel_wanted(
+    index: CagraIndex, Qt: torch.Tensor, k: int, itopk: int, width: int
+) -> bool:
+    """Route the graph search through the `cagra_search` kernel? On the GPU,
+    for f32 inputs within the wrapper's limits (k <= itopk <= 512, d <= 2048,
+    deg <= 128, search_width * deg <= 2048, its LDS budget).
+    SRML_CAGRA_KERNEL=0 forces the torch search; =1 asks for the kernel, which
+    it gets wherever it is legal; unset takes the measured default. On a GPU
+    without the built extension the kernel path raises, as every HIP path."""
+    from ..ops.dispatch import use_hip
+
+    env = os.environ.get("SRML_CAGRA_KERNEL")
+    if env == "0" or not (Qt.is_cuda and use_hip(Qt, index.Xt)):
+        return False
+    if Qt.dtype != torch.float32 or index.Xt.dtype != torch.float32:
+        return False
+    n, d = index.Xt.shape
+    deg = index.G.shape[1]
+    if not (1 <= k <= itopk <= 512 and 1 <= d <= 2048 and 1 <= deg <= 128):
+        return False
+    if width * deg > 2048 or n >= 2**31:
+        return False
+    slots = _pow2_ceil(2 * (itopk + width * deg))
+    lds = (
+        _pow2_ceil(itopk + width * deg) * 8
+        + slots * 4
+        + (min(width, itopk) + 3) // 4 * 16
+        + (d + 3) // 4 * 16
+    )
+    if lds > _CAGRA_LDS_BUDGET:
+        return False
+    return env == "1" or _CAGRA_KERNEL_DEFAULT
+
+
+def _cagra_query(
+    index: CagraIndex, Qt: torch.Tensor, k: int, itopk: int, width: int, max_it: int
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Search the kept graph from itopk random seeds per query (CPU generator,
+    seed 11, the same on both paths). Returns (squared-L2 keys, item rows):
+    the fused kernel where `_cagra_kernel_wanted` says so, with (+inf, -1) in
+    slots it could not fill, `_graph_beam_search` otherwise."""
+    if not _cagra_kernel_wanted(index, Qt, k, itopk, width):
+        if index.G64 is None:  # torch indexing wants i64: cast once, not per call
+            index.G64 = index.G.to(torch.int64)
+        return _graph_beam_search(Qt, index.Xt, index.G64, k, itopk, max_it, expand=width)
+    keys, ids, _ = _cagra_search_kernel(index, Qt, k, itopk, width, max_it)
+    return keys, ids.to(torch.int64)
+
+
+def _cagra_search_kernel(
+    index: CagraIndex, Qt: torch.Tensor, k: int, itopk: int, width: int, max_it: int
+) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Kernel path of `_cagra_query`: one block per query, the whole search
+    in one launch. Returns (keys, i32 item rows, stats [nq, 3] = iterations,
+    distance evaluations, visited-filter resets per query)."""
+    from ..ops.dispatch import hip_ops
+
+    nq, n = Qt.shape[0], index.Xt.shape[0]
+    seeds = index.seeds
+    # the seeds depend on (nq, itopk) alone: repeated calls of one shape reuse them
+    if seeds is None or tuple(seeds.shape) != (nq, itopk) or seeds.device != Qt.device:
+        g = torch.Generator(device="cpu")
+        g.manual_seed(11)
+        seeds = torch.randint(0, n, (nq, itopk), generator=g).to(torch.int32).to(Qt.device)
+        index.seeds = seeds
+    return hip_ops().cagra_search(
+        Qt.contiguous(), index.Xt.contiguous(), index.G, seeds, k, itopk, width, max_it, 0
+    )
 
 
 def _pq_encode(resid: torch.Tensor, m_sub: int, n_codes: int = 256, iters: int = 8):

@@ -35,7 +35,8 @@ TAIL = """## Metrics
 
 `cosine` normalises every row by `max(norm, 1e-30)`: a zero vector stays \
 zero and comes out at cosine distance 0.5 from everything. An empty slot \
-appears when fewer than `k` items are reachable through the probed lists. \
+appears when fewer than `k` items are reachable through the probed lists \
+(or, for cagra, through the graph). \
 Exact `NearestNeighbors` has no metric parameter (Euclidean, as in the \
 reference).
 
@@ -57,8 +58,31 @@ model and per rank. `SRML_ANN_CACHE=0` builds on every call. On the GPU the \
 ADC scan runs the `ivfpq_scan_topk` kernel (f32, `k * refine_ratio <= 256`, \
 `M * 2**n_bits * 4` bytes of lookup table within the 144 KB LDS budget, i.e. \
 `M <= 128` at 8 bits); `SRML_IVFPQ_KERNEL=0` forces the torch scan, which \
-also serves every case the kernel does not take. ivfflat and cagra still \
-build per call.
+also serves every case the kernel does not take.
+
+ivfflat keeps its coarse index (`nlist` k-means lists) the same way, under \
+`nlist` and the metric; `nprobe` is a search parameter and never rebuilds.
+
+`algoParams` of `algorithm="cagra"`:
+
+| key | default | meaning |
+|---|---|---|
+| `graph_degree` | 32 | forward edges per node of the nn-descent graph; `graph_degree // 2` reverse edges are appended (build) |
+| `nn_descent_niter` | 3 | nn-descent rounds (build) |
+| `itopk_size` | `max(64, 2k)` | entries kept during the search; rounded up to a multiple of 32, and a rounded value below `k` raises `ValueError` before any work (reference knn.py:1350-1359) |
+| `search_width` | `max(4, itopk_size // 8)` | entries expanded per iteration. cuVS defaults to 1; at width 1 and 10 iterations recall@10 at 20000x64 falls to 0.63, so the default stays the width the search has always used |
+| `max_iterations` | 0 | 0 or absent: `ceil(itopk_size / search_width) + 10`; the search stops earlier once every kept entry has been expanded |
+
+A cagra model builds its graph in the first `kneighbors` call and keeps it \
+under the two build parameters (and the metric): changing `itopk_size`, \
+`search_width` or `max_iterations` between calls never rebuilds. On the GPU \
+the search is the `cagra_search` kernel (f32, `k <= itopk_size <= 512`, \
+`d <= 2048`, graph rows of at most 128 entries, `search_width * row <= 2048`): \
+one block per query keeps the itopk list, the candidates and a visited filter \
+in LDS, keys every node once per filter period and never re-expands a node. \
+`SRML_CAGRA_KERNEL=0` forces the torch beam search, which also serves the \
+CPU and every case outside those limits with the same parameters. Slots the \
+search could not fill report id `-1` and `+inf`.
 
 `DBSCAN(metric=...)` (reference clustering.py:761):
 
