@@ -2939,6 +2939,180 @@ __global__ __launch_bounds__(256) void cagra_search_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// cagra_prune: rank-based detour counting and reordering of a kNN graph
+// (cuVS cagra's graph optimisation, first half). G is [n, D] item ids, row u
+// in ascending distance order. Integer-only, so the result does not depend on
+// the order in which the LDS atomics land:
+//   entry j of row u is dead if G[u][j] == u or repeats an earlier entry;
+//   detour[u][j] = #{ i < j : i live, G[u][j] in set(G[G[u][i]]) }, -1 if dead;
+//   P[u] = live entries by (detour, j), first D_out, padded with u.
+// One wave per node in a 64-thread block: every phase boundary is then a
+// barrier of that wave alone, and no wave waits for another node's live
+// count. Per node, in LDS (ints): the row, an open-addressed id -> first rank
+// table of 2 * pow2ceil(D) slots (linear probing, -1 = empty, load <= 1/2),
+// cnt[D] and last[D], the live ranks compacted in order, and pow2ceil(D) sort
+// keys (detour << 9 | j). For each live i in rank order the lanes read
+// neighbour i's row coalesced and probe the table; a hit at rank j > i swaps
+// i into last[j] and bumps cnt[j] unless i was already there, so a neighbour
+// that holds the id twice counts once. That needs the table updates of one i
+// to precede those of the next: the loads of CP_BATCH neighbour rows are
+// issued together (they are dependent gathers), the probes then run one row
+// after the other in program order, and a wave's LDS operations complete in
+// order. An id outside [0, n) is never dereferenced (it is treated as dead);
+// ids in range are the caller's precondition.
+// Reference: cuVS cagra::optimize (knn.py:978-982).
+// ---------------------------------------------------------------------------
+
+constexpr int CP_MAX_D = 256;
+constexpr int CP_BATCH = 4;
+constexpr int CP_DEAD_KEY = 0x7fffffff;
+
+static inline int64_t cagra_prune_lds_bytes(int64_t D) {
+  const int64_t p2 = cg_pow2_ceil(D);
+  return (4 * D + 5 * p2) * 4;  // row, cnt, last, liv | 2 tables of 2*p2 | keys
+}
+
+// slot of `id` in the table, or -1. Read-only; an empty slot ends the probe.
+__device__ inline int cp_find(const int* tab_id, unsigned mask, int shift, int id) {
+  unsigned h = ((unsigned)id * 2654435761u) >> shift;
+  for (unsigned probe = 0; probe <= mask; ++probe) {
+    const int s = (int)(h & mask);
+    const int got = tab_id[s];
+    if (got == id) return s;
+    if (got == -1) return -1;
+    ++h;
+  }
+  return -1;
+}
+
+template <int CH>  // CH = ceil(D / 64) row entries per lane
+__global__ __launch_bounds__(64) void cagra_prune_kernel(
+    const int* __restrict__ G,   // [n, D]
+    int n, int D, int D_out, int p2, int tab_bits,
+    int* __restrict__ P,         // [n, D_out]
+    int* __restrict__ detour) {  // [n, D]
+  extern __shared__ __attribute__((aligned(16))) unsigned char cp_smem[];
+  int* row = reinterpret_cast<int*>(cp_smem);
+  int* cnt = row + D;
+  int* last = cnt + D;
+  int* liv = last + D;
+  int* tab_id = liv + D;
+  const int slots = 2 * p2;
+  int* tab_rank = tab_id + slots;
+  int* keys = tab_rank + slots;
+
+  const int lane = threadIdx.x;
+  const unsigned mask = (unsigned)slots - 1u;
+  const int shift = 32 - tab_bits;
+
+  for (int64_t u64 = blockIdx.x; u64 < n; u64 += gridDim.x) {
+    const int u = (int)u64;
+    // ---- 0. the row, cleared counters and table
+    for (int j = lane; j < D; j += 64) {
+      row[j] = G[(size_t)u * D + j];
+      cnt[j] = 0;
+      last[j] = -1;
+    }
+    for (int s = lane; s < slots; s += 64) {
+      tab_id[s] = -1;
+      tab_rank[s] = CP_DEAD_KEY;
+    }
+    __syncthreads();
+    // ---- 1. id -> first rank
+    for (int j = lane; j < D; j += 64) {
+      const int id = row[j];
+      if (id == u || id < 0 || id >= n) continue;
+      unsigned h = ((unsigned)id * 2654435761u) >> shift;
+      for (unsigned probe = 0; probe <= mask; ++probe) {
+        const int s = (int)(h & mask);
+        const int old = atomicCAS(&tab_id[s], -1, id);
+        if (old == -1 || old == id) {
+          atomicMin(&tab_rank[s], j);
+          break;
+        }
+        ++h;
+      }
+    }
+    __syncthreads();
+    // ---- 2. live ranks, compacted in order; a dead entry reports -1
+    int nlive = 0;
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+      const int j = c * 64 + lane;
+      bool live = false;
+      if (j < D) {
+        const int id = row[j];
+        if (id != u && id >= 0 && id < n) {
+          const int s = cp_find(tab_id, mask, shift, id);
+          live = s >= 0 && tab_rank[s] == j;
+        }
+        if (!live) cnt[j] = -1;
+      }
+      const unsigned long long m = __ballot(live);
+      if (live) liv[nlive + __popcll(m & ((1ull << lane) - 1ull))] = j;
+      nlive += __popcll(m);
+    }
+    __syncthreads();
+    // ---- 3. detour counts
+    for (int t0 = 0; t0 < nlive; t0 += CP_BATCH) {  // wave-uniform trip count
+      int vals[CP_BATCH][CH];
+      int rank_i[CP_BATCH];
+#pragma unroll
+      for (int b = 0; b < CP_BATCH; ++b) {
+        const bool on = t0 + b < nlive;
+        rank_i[b] = on ? liv[t0 + b] : -1;
+        const int nb = on ? row[rank_i[b]] : 0;
+        const int* nrow = G + (size_t)nb * D;
+#pragma unroll
+        for (int c = 0; c < CH; ++c) {
+          const int e = c * 64 + lane;
+          vals[b][c] = (on && e < D) ? nrow[e] : -1;
+        }
+      }
+#pragma unroll
+      for (int b = 0; b < CP_BATCH; ++b) {
+        const int i = rank_i[b];
+#pragma unroll
+        for (int c = 0; c < CH; ++c) {
+          const int id = vals[b][c];
+          if (id < 0 || id >= n) continue;
+          const int s = cp_find(tab_id, mask, shift, id);
+          if (s < 0) continue;
+          const int j = tab_rank[s];
+          if (j > i && atomicExch(&last[j], i) != i) atomicAdd(&cnt[j], 1);
+        }
+      }
+    }
+    __syncthreads();
+    // ---- 4. detour out, then the live entries by (detour, rank)
+    for (int j = lane; j < D; j += 64) detour[(size_t)u * D + j] = cnt[j];
+    for (int j = lane; j < p2; j += 64)
+      keys[j] = (j < D && cnt[j] >= 0) ? ((cnt[j] << 9) | j) : CP_DEAD_KEY;
+    __syncthreads();
+    for (int k2 = 2; k2 <= p2; k2 <<= 1) {
+      for (int jj = k2 >> 1; jj > 0; jj >>= 1) {
+        for (int i = lane; i < (p2 >> 1); i += 64) {
+          const int lo = ((i & ~(jj - 1)) << 1) | (i & (jj - 1));
+          const int hi = lo | jj;
+          const bool asc = (lo & k2) == 0;
+          const int a = keys[lo], b = keys[hi];
+          if ((a > b) == asc) {
+            keys[lo] = b;
+            keys[hi] = a;
+          }
+        }
+        __syncthreads();
+      }
+    }
+    for (int k = lane; k < D_out; k += 64) {
+      const int key = keys[k];
+      P[(size_t)u * D_out + k] = key == CP_DEAD_KEY ? u : row[key & 511];
+    }
+    __syncthreads();  // the next node rewrites everything
+  }
+}
+
+// ---------------------------------------------------------------------------
 // CSR GLM kernels (the reference's LogisticRegressionMG sparse path,
 // classification.py:960-966, runs cuML SpMM; torch/rocSPARSE here spent its
 // time in f64 index_add column stats, a 400M-pair radix-sort transpose and
@@ -4067,6 +4241,38 @@ std::vector<torch::Tensor> cagra_search(torch::Tensor Q, torch::Tensor X, torch:
   return {keys, ids, stats};
 }
 
+// (P [n, D_out] i32, detour [n, D] i32) of the graph pruning specified above
+// cagra_prune_kernel.
+std::vector<torch::Tensor> cagra_prune(torch::Tensor G, int64_t D_out) {
+  TORCH_CHECK(G.is_cuda() && G.dtype() == torch::kInt32 && G.is_contiguous() && G.dim() == 2,
+              "cagra_prune: G must be a contiguous 2-d i32 device tensor");
+  const int64_t n = G.size(0), D = G.size(1);
+  TORCH_CHECK(n < (1LL << 31), "cagra_prune supports n < 2**31");
+  TORCH_CHECK(D >= 1 && D <= CP_MAX_D, "cagra_prune supports 1 <= D <= 256");
+  TORCH_CHECK(D_out >= 1 && D_out <= D, "cagra_prune supports 1 <= D_out <= D");
+  auto P = torch::empty({n, D_out}, G.options());
+  auto detour = torch::empty({n, D}, G.options());
+  if (n > 0) {
+    const int64_t p2 = cg_pow2_ceil(D);
+    int bits = 0;
+    while ((1LL << bits) < 2 * p2) ++bits;
+    const size_t lds = (size_t)cagra_prune_lds_bytes(D);
+    const unsigned grid = (unsigned)std::min<int64_t>(n, 1LL << 20);
+#define CAGRA_PRUNE_LAUNCH(CH)                                                              \
+  hipLaunchKernelGGL(cagra_prune_kernel<CH>, dim3(grid), dim3(64), lds, cur_stream(),       \
+                     G.data_ptr<int32_t>(), (int)n, (int)D, (int)D_out, (int)p2, bits,      \
+                     P.data_ptr<int32_t>(), detour.data_ptr<int32_t>())
+    const int ch = (int)((D + 63) / 64);
+    if (ch == 1) CAGRA_PRUNE_LAUNCH(1);
+    else if (ch == 2) CAGRA_PRUNE_LAUNCH(2);
+    else if (ch == 3) CAGRA_PRUNE_LAUNCH(3);
+    else CAGRA_PRUNE_LAUNCH(4);
+#undef CAGRA_PRUNE_LAUNCH
+    C10_HIP_KERNEL_LAUNCH_CHECK();
+  }
+  return {P, detour};
+}
+
 torch::Tensor fil_predict(torch::Tensor X, torch::Tensor feat, torch::Tensor thr,
                           torch::Tensor left, torch::Tensor right, torch::Tensor value,
                           torch::Tensor roots, bool classif) {
@@ -4208,5 +4414,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("Q"), py::arg("X"), py::arg("G"), py::arg("seeds"), py::arg("k"),
         py::arg("itopk"), py::arg("search_width"), py::arg("max_iterations"),
         py::arg("hash_bits") = 0);
+  m.def("cagra_prune", &cagra_prune,
+        "rank-based detour counts of a kNN graph and its rows reordered by them",
+        py::arg("G"), py::arg("D_out"));
   m.attr("_is_hip") = true;
 }

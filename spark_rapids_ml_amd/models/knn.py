@@ -28,6 +28,7 @@ from __future__ import annotations
 
 import math
 import os
+import warnings
 from dataclasses import dataclass
 from typing import Any, Dict, Optional, Tuple
 
@@ -373,7 +374,8 @@ class _ANNParams(_NNParams):
         "ann",
         "algorithm",
         "ivfflat|ivfpq|cagra (reference knn.py:1485-1524). cagra algoParams: "
-        "graph_degree, nn_descent_niter (build); itopk_size, search_width, "
+        "graph_degree, nn_descent_niter, intermediate_graph_degree, "
+        "build_algo (build); itopk_size, search_width, "
         "max_iterations (search).",
         TypeConverters.toString,
     )
@@ -509,8 +511,11 @@ class ApproximateNearestNeighborsModel(_ANNModelParams, _NNModelBase):
         expands search_width of them per iteration. The graph
         (`_cagra_build`) is kept across calls by `_cached_index` under its
         build parameters alone, so the search parameters can change freely;
-        each call runs `_cagra_query` on it."""
+        each call runs `_cagra_query` on it. With `intermediate_graph_degree`
+        or `build_algo` in algoParams the graph is cuVS's optimised one
+        (`_cagra_optimize_params`), and the two resolved values join the key."""
         _cagra_search_params(algo_params, self.getK())  # fails before any work
+        _cagra_optimize_params(algo_params, warn=False)  # as does a bad build parameter
 
         def search(Qt: torch.Tensor, X: np.ndarray, k: int):
             from ..parallel.context import get_comm
@@ -525,6 +530,10 @@ class ApproximateNearestNeighborsModel(_ANNModelParams, _NNModelBase):
                 "graph_degree": int(algo_params.get("graph_degree", 32)),
                 "nn_descent_niter": int(algo_params.get("nn_descent_niter", 3)),
             }
+            optimize = _cagra_optimize_params(algo_params, X.shape[0], warn=False)
+            if optimize is not None:
+                build_params["intermediate_graph_degree"] = optimize[1]
+                build_params["build_algo"] = optimize[2]
             index = self._cached_index("cagra", build_params, metric, build)
             itopk, width, max_it = _cagra_search_params(algo_params, k)
             return _cagra_query(index, Qt, k, itopk, width, max_it)
@@ -894,19 +903,233 @@ class CagraIndex:
 
     Xt: torch.Tensor  # [n, d] items
     G: torch.Tensor  # [n, deg] i32 search graph: forward edges, then the
-    # capped reverse edges (filler = the node itself)
+    # capped reverse edges (filler = the node itself); the optimised build's
+    # pruned and reverse-merged rows are exactly graph_degree wide
     G64: Optional[torch.Tensor] = None  # i64 copy, made when the torch search first runs
     seeds: Optional[torch.Tensor] = None  # [nq, itopk] i32 seeds of the last kernel search
 
 
 def _cagra_build(Xt: torch.Tensor, algo_params: Dict[str, Any]) -> CagraIndex:
     """nn-descent graph of `graph_degree` forward edges, augmented with
-    graph_degree // 2 reverse edges per node (cagra's "optimize" step)."""
-    degree = int(algo_params.get("graph_degree", 32))
+    graph_degree // 2 reverse edges per node. With `intermediate_graph_degree`
+    or `build_algo` in algoParams, cuVS's build instead: a kNN graph of the
+    intermediate degree (`_cagra_knn_graph`), pruned by detour counts and
+    merged with its reverse edges at exactly `graph_degree` columns
+    (`_cagra_optimize`)."""
     build_iters = int(algo_params.get("nn_descent_niter", 3))
+    optimize = _cagra_optimize_params(algo_params, Xt.shape[0])
+    if optimize is not None:
+        degree, inter, build_algo = optimize
+        G = _cagra_knn_graph(Xt, inter, build_algo, build_iters)
+        return CagraIndex(Xt=Xt, G=_cagra_optimize(G, degree))
+    degree = int(algo_params.get("graph_degree", 32))
     G = _nn_descent(Xt, degree, build_iters)
     G_search = torch.cat([G, _reverse_edges(G, degree // 2)], dim=1)
     return CagraIndex(Xt=Xt, G=G_search.to(torch.int32).contiguous())
+
+
+_CAGRA_BUILD_ALGOS = ("nn_descent", "ivf_pq")
+_CAGRA_PRUNE_MAX_D = 256  # cagra_prune: widest row the kernel takes
+_CAGRA_PRUNE_CHUNK_ELEMS = 1 << 22  # torch prune: rows * D * D per chunk (32 MiB of i64)
+
+
+def _cagra_optimize_params(
+    algo_params: Dict[str, Any], n: Optional[int] = None, warn: bool = True
+) -> Optional[Tuple[int, int, str]]:
+    """(graph_degree, intermediate_graph_degree, build_algo) of the optimised
+    build, or None when algoParams names neither `intermediate_graph_degree`
+    nor `build_algo` (the build stays as it was). The intermediate degree
+    defaults to 2 * graph_degree (cuVS's 128 / 64). As in cuVS, a graph_degree
+    above it is lowered to it, and with `n` given an intermediate degree >= n
+    is lowered to n - 1 and graph_degree with it, each with a RuntimeWarning
+    unless `warn` is off. build_algo is nn_descent (the default here; the
+    reference defaults to ivf_pq, docs/parity.md) or ivf_pq, which takes an
+    intermediate degree below 256 (reference knn.py:1600)."""
+    if "intermediate_graph_degree" not in algo_params and "build_algo" not in algo_params:
+        return None
+    build_algo = algo_params.get("build_algo", "nn_descent")
+    if build_algo not in _CAGRA_BUILD_ALGOS:
+        raise ValueError(
+            f"cagra build_algo must be 'nn_descent' or 'ivf_pq', got {build_algo!r}"
+        )
+    degree = int(algo_params.get("graph_degree", 32))
+    inter = int(algo_params.get("intermediate_graph_degree", 2 * degree))
+    if degree < 1 or inter < 1:
+        raise ValueError(
+            "cagra graph_degree and intermediate_graph_degree must be >= 1, got "
+            f"{degree} and {inter}"
+        )
+    if build_algo == "ivf_pq" and inter >= 256:
+        raise ValueError(
+            "cagra with ivf_pq build_algo expects intermediate_graph_degree "
+            f"({inter}) to be smaller than 256"
+        )
+    if n is not None and inter >= n:
+        lowered = max(1, n - 1)
+        if warn:
+            warnings.warn(
+                f"cagra intermediate_graph_degree ({inter}) must be below the number "
+                f"of items ({n}); lowered to {lowered}",
+                RuntimeWarning,
+            )
+        inter = lowered
+    if degree > inter:
+        if warn:
+            warnings.warn(
+                f"cagra graph_degree ({degree}) cannot exceed "
+                f"intermediate_graph_degree ({inter}); lowered to {inter}",
+                RuntimeWarning,
+            )
+        degree = inter
+    return degree, inter, build_algo
+
+
+def _cagra_knn_graph(Xt: torch.Tensor, degree: int, build_algo: str, n_iter: int) -> torch.Tensor:
+    """The intermediate kNN graph of the optimised build, [n, degree] int64,
+    each row in ascending distance order: nn-descent, or an IVF-PQ index of
+    the items queried with the items themselves."""
+    if build_algo == "nn_descent":
+        return _nn_descent(Xt, degree, n_iter)
+    return _ivfpq_knn_graph(Xt, degree)
+
+
+# Build-time IVF-PQ search of `_ivfpq_knn_graph`: at normal 2000 x 16, degree
+# 64, the graph's recall against the exact kNN graph was 0.28 at nlist // 16
+# probed lists, 0.74 at nlist // 4 and 0.92 at nlist // 2 (RESULTS.md).
+_CAGRA_IVFPQ_REFINE = 2.0
+
+
+def _ivfpq_knn_graph(Xt: torch.Tensor, degree: int) -> torch.Tensor:
+    """kNN graph through `_ivfpq_build` with default parameters: every item
+    asks for degree + 1 neighbours over nlist // 2 probed lists with the exact
+    refine, in row chunks that keep the refine's [q, k_cand, d] gather near
+    1 GiB. A row drops its own id (its last entry when the search missed the
+    item itself); an unfilled slot becomes the row's own id, which the prune
+    treats as dead. Rows are in exact-distance order."""
+    n, d = Xt.shape
+    index = _ivfpq_build(Xt, {}, "sqeuclidean")
+    nlist = index.boundaries.numel() - 1
+    nprobe = max(1, nlist // 2)
+    k = min(n, degree + 1)
+    k_cand = min(n, max(k, int(k * _CAGRA_IVFPQ_REFINE)))
+    chunk = max(1, (1 << 30) // (k_cand * d * 4))
+    G = torch.empty((n, k - 1), dtype=torch.int64, device=Xt.device)
+    cols = torch.arange(k, device=Xt.device)[None, :]
+    for s in range(0, n, chunk):
+        e = min(n, s + chunk)
+        _, ids = _ivfpq_query(index, Xt[s:e].contiguous(), k, nprobe, _CAGRA_IVFPQ_REFINE)
+        own = torch.arange(s, e, device=Xt.device)[:, None]
+        is_own = ids == own
+        drop = torch.where(is_own.any(dim=1), is_own.int().argmax(dim=1), k - 1)
+        kept = ids[cols != drop[:, None]].view(e - s, k - 1)
+        G[s:e] = torch.where(kept < 0, own, kept)
+    return G
+
+
+def _cagra_optimize(G: torch.Tensor, degree: int) -> torch.Tensor:
+    """cuVS's graph optimisation: rank-based pruning of the intermediate graph
+    to `degree` columns, then the reverse-edge merge. [n, degree] i32."""
+    P, _ = _cagra_prune(G, degree)
+    return _cagra_merge_reverse(P).to(torch.int32).contiguous()
+
+
+def _cagra_prune_kernel_wanted(G: torch.Tensor) -> bool:
+    """Route the pruning through the `cagra_prune` kernel? On the GPU, for
+    rows of at most 256 ids. SRML_CAGRA_PRUNE_KERNEL=0 forces the torch
+    formulation. On a GPU without the built extension the kernel path raises,
+    as every HIP path."""
+    from ..ops.dispatch import use_hip
+
+    if os.environ.get("SRML_CAGRA_PRUNE_KERNEL") == "0":
+        return False
+    if not (G.is_cuda and use_hip(G)):
+        return False
+    return G.shape[1] <= _CAGRA_PRUNE_MAX_D and G.shape[0] < 2**31
+
+
+def _cagra_prune(G: torch.Tensor, d_out: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Rank-based detour pruning of a kNN graph G [n, D] whose rows are in
+    ascending distance order. Entry j of row u is dead if it is u itself or
+    repeats an earlier entry; a live j has
+    detour[u][j] = #{i < j : i live and G[u][j] in set(G[G[u][i]])}, a dead
+    one -1. P[u] is the live entries by (detour, j), cut to d_out and padded
+    with u. Integer-only, the same on the kernel and the torch path.
+    Returns (P [n, d_out] int64, detour [n, D] int32)."""
+    n, D = G.shape
+    if not 1 <= d_out <= D:
+        raise ValueError(f"cagra prune needs 1 <= D_out <= D, got {d_out} and {D}")
+    if _cagra_prune_kernel_wanted(G):
+        from ..ops.dispatch import hip_ops
+
+        P, detour = hip_ops().cagra_prune(G.to(torch.int32).contiguous(), d_out)
+        return P.to(torch.int64), detour
+    G = G.to(torch.int64)
+    device = G.device
+    P = torch.empty((n, d_out), dtype=torch.int64, device=device)
+    detour = torch.empty((n, D), dtype=torch.int32, device=device)
+    before = torch.ones((D, D), dtype=torch.bool, device=device).triu(1)  # [i, j]: i < j
+    ranks = torch.arange(D, device=device)
+    # the [rows, D, D] neighbour-row gather and its searchsorted temporaries
+    chunk = max(1, _CAGRA_PRUNE_CHUNK_ELEMS // (D * D))
+    for s in range(0, n, chunk):
+        e = min(n, s + chunk)
+        ids = G[s:e]
+        own = torch.arange(s, e, device=device)[:, None]
+        sid, order = torch.sort(ids, dim=1, stable=True)
+        dup_s = torch.zeros_like(sid, dtype=torch.bool)
+        dup_s[:, 1:] = sid[:, 1:] == sid[:, :-1]
+        dup = torch.zeros_like(dup_s).scatter_(1, order, dup_s)
+        live = ~dup & (ids != own)
+        # hit[r, i, j]: G[u][j] occurs in neighbour i's raw row
+        nbr = torch.sort(G[ids], dim=2).values  # [r, D(i), D]
+        want = ids[:, None, :].expand(-1, D, -1).contiguous()  # [r, D(i), D(j)]
+        at = torch.searchsorted(nbr, want).clamp(max=D - 1)
+        hit = nbr.gather(2, at) == want
+        hit &= live[:, :, None] & before[None]
+        cnt = hit.sum(dim=1).to(torch.int32)
+        cnt = torch.where(live, cnt, torch.full_like(cnt, -1))
+        detour[s:e] = cnt
+        key = torch.where(live, cnt.to(torch.int64) * 512 + ranks, 1 << 40)
+        skey, sel = torch.sort(key, dim=1)
+        picked = ids.gather(1, sel[:, :d_out])
+        P[s:e] = torch.where(skey[:, :d_out] < (1 << 40), picked, own)
+    return P, detour
+
+
+def _cagra_merge_reverse(P: torch.Tensor) -> torch.Tensor:
+    """Reverse-edge merge of a pruned graph P [n, D_out] (filler = the row's
+    own id). Edges u -> P[u][k] are taken in (k, u) order, so the strongest
+    edges claim a node's reverse slots first; rev[v] is the first D_out
+    sources that reach v. F[u] is the first D_out distinct ids other than u
+    of P[u][:D_out // 2] ++ rev[u] ++ P[u][D_out // 2:], padded with u.
+    Returns F [n, D_out] int64."""
+    n, d_out = P.shape
+    P = P.to(torch.int64)
+    device = P.device
+    h = d_out // 2
+    own = torch.arange(n, device=device)
+    dst = P.t().reshape(-1)  # (k, u) order
+    src = own.repeat(d_out)
+    real = dst != src
+    dst, src = dst[real], src[real]
+    order = torch.argsort(dst, stable=True)
+    dst_s, src_s = dst[order], src[order]
+    firsts = torch.searchsorted(dst_s, own)
+    pos = torch.arange(dst_s.numel(), device=device) - firsts[dst_s]
+    keep = pos < d_out
+    rev = own[:, None].repeat(1, d_out)  # a copy also at d_out = 1
+    rev[dst_s[keep], pos[keep]] = src_s[keep]
+    cat = torch.cat([P[:, :h], rev, P[:, h:]], dim=1)  # [n, 2 * d_out]
+    # first occurrence of every id other than the row's own, in column order
+    sid, order = torch.sort(cat, dim=1, stable=True)
+    dup_s = torch.zeros_like(sid, dtype=torch.bool)
+    dup_s[:, 1:] = sid[:, 1:] == sid[:, :-1]
+    dup = torch.zeros_like(dup_s).scatter_(1, order, dup_s)
+    good = ~dup & (cat != own[:, None])
+    cols = torch.arange(cat.shape[1], device=device)[None, :]
+    skey, sel = torch.sort(torch.where(good, cols, cat.shape[1]), dim=1)
+    picked = cat.gather(1, sel[:, :d_out])
+    return torch.where(skey[:, :d_out] < cat.shape[1], picked, own[:, None])
 
 
 def _cagra_search_params(algo_params: Dict[str, Any], k: int) -> Tuple[int, int, int]:

@@ -69,13 +69,23 @@ ivfflat keeps its coarse index (`nlist` k-means lists) the same way, under \
 |---|---|---|
 | `graph_degree` | 32 | forward edges per node of the nn-descent graph; `graph_degree // 2` reverse edges are appended (build) |
 | `nn_descent_niter` | 3 | nn-descent rounds (build) |
+| `intermediate_graph_degree` | absent; `2 * graph_degree` once `build_algo` is given | present (or with `build_algo`): the optimised build. A kNN graph of this many edges per node is pruned by rank-based detour counts to `graph_degree` columns and merged with its reverse edges, so the search graph is exactly `graph_degree` wide. A `graph_degree` above it is lowered to it, and a value `>= n` is lowered to `n - 1` (and `graph_degree` with it), each with a `RuntimeWarning` (build) |
+| `build_algo` | absent; `"nn_descent"` once `intermediate_graph_degree` is given | `"nn_descent"` or `"ivf_pq"` (an IVF-PQ index of the items with default parameters, queried with the items over `nlist // 2` lists with refine ratio 2); anything else raises `ValueError`. `"ivf_pq"` with `intermediate_graph_degree >= 256` raises the reference's `ValueError`. The reference defaults to `"ivf_pq"` (docs/parity.md) (build) |
+| `compression` | - | not supported: the key is ignored, the items stay f32 |
 | `itopk_size` | `max(64, 2k)` | entries kept during the search; rounded up to a multiple of 32, and a rounded value below `k` raises `ValueError` before any work (reference knn.py:1350-1359) |
 | `search_width` | `max(4, itopk_size // 8)` | entries expanded per iteration. cuVS defaults to 1; at width 1 and 10 iterations recall@10 at 20000x64 falls to 0.63, so the default stays the width the search has always used |
 | `max_iterations` | 0 | 0 or absent: `ceil(itopk_size / search_width) + 10`; the search stops earlier once every kept entry has been expanded |
 
 A cagra model builds its graph in the first `kneighbors` call and keeps it \
-under the two build parameters (and the metric): changing `itopk_size`, \
-`search_width` or `max_iterations` between calls never rebuilds. On the GPU \
+under `graph_degree` and `nn_descent_niter` (and the metric), plus the \
+resolved `intermediate_graph_degree` and `build_algo` when either is given: \
+changing `itopk_size`, `search_width` or `max_iterations` between calls never \
+rebuilds. With neither of the two keys the build is the one it has always \
+been (`graph_degree` forward + `graph_degree // 2` reverse columns). In the \
+optimised build the pruning is the `cagra_prune` kernel on the GPU (rows of \
+at most 256 ids; `SRML_CAGRA_PRUNE_KERNEL=0` forces the torch formulation, \
+which gives the same integers and serves the CPU); the reverse-edge merge is \
+torch on both devices. On the GPU \
 the search is the `cagra_search` kernel (f32, `k <= itopk_size <= 512`, \
 `d <= 2048`, graph rows of at most 128 entries, `search_width * row <= 2048`): \
 one block per query keeps the itopk list, the candidates and a visited filter \
