@@ -1846,6 +1846,315 @@ __global__ __launch_bounds__(256) void kmeans_refine_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// kmeans_step_resident: a whole Lloyd step (labels, per-centre sums, counts,
+// inertia) in ONE pass over X for small k·d, the centres resident in LDS.
+// No [n, k] dot block reaches global memory and X is read from HBM once.
+//
+// Persistent: 256 threads, one block per CU, blocks stride over 64-row tiles.
+// LDS (dynamic): centres cs[k_pad][ld] f32 (k_pad = ceil32(k), loaded once,
+// pad rows zero), the row tile xs[64][ld], c_sq[k_pad] (from the LDS copy;
+// +inf for pad centres so they never win), the tile's labels, the block's
+// integer counts and the per-parity argmin partials. ld = ceil2(d) + 1: odd,
+// so the 32 lanes of an MFMA operand read, which walk ROWS of cs / xs, hit
+// 32 different banks; columns [d, ld) stay zero (the K tail of the dots and
+// the clamp target of the accumulate's column reads).
+//
+// Per tile:
+//   stage   the tile is contiguous in X: float4 global loads (scalar when
+//           d % 4 != 0) into xs. Up to d = 256 the NEXT tile's loads are
+//           issued into registers here and land in LDS one tile later, so the
+//           HBM latency hides under both MFMA phases.
+//   dots    mfma_f32_32x32x2f32, centres = M, rows = N. Wave w takes the row
+//           half w & 1 and the centre tiles of parity w >> 1; a lane holds 16
+//           centres of ONE row per tile, so the argmin of c_sq - 2·dot runs in
+//           registers, one lane^32 exchange finishes the wave's share and the
+//           two parities meet through LDS. Lowest index wins an exact tie.
+//   update  64 threads: label out, d2 = max(key + x_sq, 0) into an f64
+//           per-thread inertia, count by LDS integer atomic.
+//   sums    sums[k_pad, d] += onehot(labels)^T · xs as a second MFMA product
+//           (M = centres, N = columns, K = the 64 rows). The one-hot operand
+//           is a compare of the row's label in LDS against the lane's centre;
+//           wave w owns column tiles [w·DW, (w+1)·DW). The KT·DW accumulator
+//           tiles stay in registers for the block's whole row range.
+// At the end each block writes one [k, d] f32 partial, one count partial and
+// one inertia partial; the host reduces them in f64. No float atomics, so a
+// fixed grid gives bit-identical results from run to run.
+// Unlike label_accumulate, where a row touches only its own centre, the
+// one-hot product multiplies EVERY centre's 0 by every row value: an Inf or
+// NaN in X makes that column of all k sums NaN (0 · Inf), not of one centre.
+// ---------------------------------------------------------------------------
+
+constexpr int KR_ROWS = 64;                       // rows per tile
+constexpr int64_t KR_LDS_BUDGET = 160 * 1024;     // gfx950 LDS per workgroup
+constexpr int KR_MAX_ACC_TILES = 8;               // KT * DW accumulator tiles per wave
+constexpr int KR_PRE_MAX_DW = 2;                  // register prefetch up to d = 256
+
+static inline int64_t kr_ld(int64_t d) { return (d + 1) / 2 * 2 + 1; }
+
+// Dynamic LDS of kmeans_step_resident_kernel, or 0 where the shape is not
+// legal: more than KR_MAX_ACC_TILES accumulator tiles per wave, or over the
+// LDS budget. ops/kmeans.py `_resident_lds_bytes` mirrors this.
+static inline int64_t kmeans_resident_lds_bytes(int64_t k, int64_t d) {
+  if (k < 1 || d < 1) return 0;
+  const int64_t k_pad = (k + 31) / 32 * 32;
+  const int64_t kt = k_pad / 32, dw = ((d + 31) / 32 + 3) / 4;
+  if (kt * dw > KR_MAX_ACC_TILES) return 0;
+  const int64_t bytes = (k_pad + KR_ROWS) * kr_ld(d) * 4  // cs + xs
+                        + k_pad * 8                       // c_sq + counts
+                        + KR_ROWS * 4                     // tile labels
+                        + 2 * KR_ROWS * 8;                // argmin partials
+  return bytes <= KR_LDS_BUDGET ? bytes : 0;
+}
+
+template <int KT, int DW>
+__global__ __launch_bounds__(256) void kmeans_step_resident_kernel(
+    const float* __restrict__ X,       // [n, d]
+    const float* __restrict__ C,       // [k, d]
+    const float* __restrict__ x_sq,    // [n]
+    int64_t n, int d, int k, int vec,  // vec: d % 4 == 0 and X 16-byte aligned
+    int32_t* __restrict__ labels,      // [n]
+    float* __restrict__ part_sums,     // [grid, k, d]
+    int32_t* __restrict__ part_cnt,    // [grid, k]
+    double* __restrict__ part_inertia) {  // [grid]
+  constexpr int K_PAD = KT * 32;
+  constexpr int T1 = (KT + 1) / 2;  // centre tiles per wave in the dots phase
+  constexpr bool PRE = DW <= KR_PRE_MAX_DW;
+  constexpr int NPRE = PRE ? DW * 8 : 1;  // float4 per thread: 64 * d / 4 / 256 <= DW * 8
+
+  extern __shared__ float kr_smem[];
+  const int ld = (int)((d + 1) / 2 * 2 + 1);
+  float* cs = kr_smem;
+  float* xs = cs + K_PAD * ld;
+  float* csq = xs + KR_ROWS * ld;
+  float* pkey = csq + K_PAD;                        // [2][64]
+  int* pidx = reinterpret_cast<int*>(pkey + 2 * KR_ROWS);  // [2][64]
+  int* lab_s = pidx + 2 * KR_ROWS;                  // [64]
+  int* cnt = lab_s + KR_ROWS;                       // [K_PAD]
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const int l31 = lane & 31;
+  const int lh = lane >> 5;
+  const int DT = (d + 31) / 32;  // column tiles that hold data
+
+  // prologue: zero cs | xs (adjacent), counts; centres in; c_sq from LDS
+  for (int e = tid; e < (K_PAD + KR_ROWS) * ld; e += 256) cs[e] = 0.0f;
+  for (int e = tid; e < K_PAD; e += 256) cnt[e] = 0;
+  __syncthreads();
+  for (int e = tid; e < k * d; e += 256) {
+    const int r = e / d;
+    cs[r * ld + (e - r * d)] = C[e];
+  }
+  __syncthreads();
+  for (int j = tid; j < K_PAD; j += 256) {
+    float s = INFINITY;
+    if (j < k) {
+      s = 0.0f;
+      for (int c = 0; c < d; ++c) s = fmaf(cs[j * ld + c], cs[j * ld + c], s);
+    }
+    csq[j] = s;
+  }
+
+  f32x16 sacc[KT][DW];
+#pragma unroll
+  for (int kt = 0; kt < KT; ++kt)
+#pragma unroll
+    for (int jt = 0; jt < DW; ++jt)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) sacc[kt][jt][r] = 0.0f;
+
+  // accumulate phase: this lane's column per slab tile, clamped onto the
+  // zero pad column ld - 1
+  int colo[DW];
+#pragma unroll
+  for (int jt = 0; jt < DW; ++jt) colo[jt] = min((wave * DW + jt) * 32 + l31, ld - 1);
+
+  // dots phase: row half, centre-tile parity and how many tiles of it exist
+  const int rh = wave & 1, par = wave >> 1;
+  const int nt = (KT - par + 1) / 2;
+  const float* xrow = xs + (rh * 32 + l31) * ld + lh;
+  const float* crow = cs + l31 * ld + lh;
+  // branch-free MFMA loop: a tile this parity does not have (odd KT) repeats
+  // the last centre tile and is ignored by the argmin
+  int coff[T1];
+#pragma unroll
+  for (int q = 0; q < T1; ++q) coff[q] = min(par + 2 * q, KT - 1) * 32 * ld;
+  const int nk2 = (d + 1) / 2;
+
+  const int64_t ntiles = (n + KR_ROWS - 1) / KR_ROWS;
+  double inert = 0.0;
+  float4 pre[NPRE];
+
+#define KR_PREFETCH(tile)                                                      \
+  do {                                                                         \
+    const int64_t r0_ = (int64_t)(tile) * KR_ROWS;                             \
+    const int nf4_ = (int)(min((int64_t)KR_ROWS, n - r0_) * d / 4);            \
+    const float4* src_ = reinterpret_cast<const float4*>(X + r0_ * d);         \
+    _Pragma("unroll") for (int q = 0; q < NPRE; ++q) {                         \
+      const int f = q * 256 + tid;                                             \
+      if (f < nf4_) pre[q] = src_[f];                                          \
+    }                                                                          \
+  } while (0)
+
+#define KR_PUT4(f, v)                                                          \
+  do {                                                                         \
+    const int e_ = (f) * 4;                                                    \
+    const int r_ = e_ / d;                                                     \
+    float* dst_ = xs + r_ * ld + (e_ - r_ * d);                                \
+    dst_[0] = (v).x; dst_[1] = (v).y; dst_[2] = (v).z; dst_[3] = (v).w;        \
+  } while (0)
+
+  if (PRE && vec) KR_PREFETCH(blockIdx.x);
+
+  for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const int64_t row0 = t * KR_ROWS;
+    const int rows = (int)min((int64_t)KR_ROWS, n - row0);
+    __syncthreads();  // prologue done / previous tile's xs and labels consumed
+    // the update threads' |x|^2, in flight while the dots run
+    const float xq = tid < rows ? x_sq[row0 + tid] : 0.0f;
+
+    // ---- stage ----
+    if (vec) {
+      const int nf4 = rows * d / 4;  // d % 4 == 0: a float4 never straddles rows
+      if (PRE) {
+#pragma unroll
+        for (int q = 0; q < NPRE; ++q) {
+          const int f = q * 256 + tid;
+          if (f < nf4) KR_PUT4(f, pre[q]);
+        }
+        if (t + gridDim.x < ntiles) KR_PREFETCH(t + gridDim.x);
+      } else {
+        const float4* src = reinterpret_cast<const float4*>(X + row0 * d);
+        for (int f = tid; f < nf4; f += 256) {
+          const float4 v = src[f];
+          KR_PUT4(f, v);
+        }
+      }
+    } else {
+      const float* src = X + row0 * d;
+      for (int e = tid; e < rows * d; e += 256) {
+        const int r = e / d;
+        xs[r * ld + (e - r * d)] = src[e];
+      }
+    }
+    if (rows < KR_ROWS) {  // last tile: rows past n must not feed 0 * stale
+      for (int e = tid; e < (KR_ROWS - rows) * d; e += 256) {
+        const int r = e / d;
+        xs[(rows + r) * ld + (e - r * d)] = 0.0f;
+      }
+    }
+    __syncthreads();
+
+    // ---- dots + per-wave argmin ----
+    {
+      f32x16 dacc[T1];
+#pragma unroll
+      for (int q = 0; q < T1; ++q)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) dacc[q][r] = 0.0f;
+#pragma unroll 4
+      for (int kk = 0; kk < nk2; ++kk) {
+        const float b = xrow[2 * kk];
+#pragma unroll
+        for (int q = 0; q < T1; ++q) {
+          const float a = crow[coff[q] + 2 * kk];
+          dacc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, dacc[q], 0, 0, 0);
+        }
+      }
+      float bk = INFINITY;
+      int bi = 0;
+#pragma unroll
+      for (int q = 0; q < T1; ++q) {
+        if (q < nt) {
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const int c = (par + 2 * q) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+            const float key = csq[c] - 2.0f * dacc[q][r];
+            if (key < bk) { bk = key; bi = c; }
+          }
+        }
+      }
+      const float ok = __shfl_xor(bk, 32, 64);
+      const int oi = __shfl_xor(bi, 32, 64);
+      if (ok < bk || (ok == bk && oi < bi)) { bk = ok; bi = oi; }
+      if (lh == 0) {
+        pkey[par * KR_ROWS + rh * 32 + l31] = bk;
+        pidx[par * KR_ROWS + rh * 32 + l31] = bi;
+      }
+    }
+    __syncthreads();
+
+    // ---- update: label, inertia, count ----
+    if (tid < KR_ROWS) {
+      float bk = pkey[tid];
+      int bi = pidx[tid];
+      const float ok = pkey[KR_ROWS + tid];
+      const int oi = pidx[KR_ROWS + tid];
+      if (ok < bk || (ok == bk && oi < bi)) { bk = ok; bi = oi; }
+      if (tid < rows) {
+        labels[row0 + tid] = bi;
+        inert += (double)fmaxf(bk + xq, 0.0f);
+        atomicAdd(&cnt[bi], 1);
+        lab_s[tid] = bi;
+      } else {
+        lab_s[tid] = -1;  // matches no centre
+      }
+    }
+    __syncthreads();
+
+    // ---- sums += onehot(labels)^T · xs ----
+    const int nkk = (rows + 1) / 2;
+#define KR_SUMS_LOOP(COND)                                                     \
+  _Pragma("unroll 2") for (int kk = 0; kk < nkk; ++kk) {                       \
+    const int row = 2 * kk + lh;                                               \
+    /* == kt * 32 where this lane's centre is the row's label */               \
+    const int rel = lab_s[row] - l31;                                          \
+    const float* xr = xs + row * ld;                                           \
+    float b[DW];                                                               \
+    _Pragma("unroll") for (int jt = 0; jt < DW; ++jt) b[jt] = xr[colo[jt]];    \
+    _Pragma("unroll") for (int kt = 0; kt < KT; ++kt) {                        \
+      const float a = rel == kt * 32 ? 1.0f : 0.0f;                            \
+      _Pragma("unroll") for (int jt = 0; jt < DW; ++jt) {                      \
+        if (COND)                                                              \
+          sacc[kt][jt] =                                                       \
+              __builtin_amdgcn_mfma_f32_32x32x2f32(a, b[jt], sacc[kt][jt], 0, 0, 0); \
+      }                                                                        \
+    }                                                                          \
+  }
+    // a wave whose whole slab holds data runs the loop without branches
+    if ((wave + 1) * DW <= DT) {
+      KR_SUMS_LOOP(true)
+    } else if (wave * DW < DT) {
+      KR_SUMS_LOOP(wave * DW + jt < DT)
+    }
+#undef KR_SUMS_LOOP
+  }
+#undef KR_PREFETCH
+#undef KR_PUT4
+
+  // ---- block partials ----
+  float* ps = part_sums + (int64_t)blockIdx.x * k * d;
+#pragma unroll
+  for (int kt = 0; kt < KT; ++kt)
+#pragma unroll
+    for (int jt = 0; jt < DW; ++jt)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int c = kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+        const int col = (wave * DW + jt) * 32 + l31;
+        if (c < k && col < d) ps[c * d + col] = sacc[kt][jt][r];
+      }
+  // the last tile's count atomics precede its post-update barrier
+  for (int j = tid; j < k; j += 256) part_cnt[(int64_t)blockIdx.x * k + j] = cnt[j];
+  if (wave == 0) {  // the update threads are exactly wave 0
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) inert += __shfl_down(inert, off, 64);
+    if (lane == 0) part_inertia[blockIdx.x] = inert;
+  }
+}
+
+// ---------------------------------------------------------------------------
 // rf_partition: counting-sort rows by batch-local node id -> (perm, seg_off).
 // Replaces the per-batch torch sort + nonzero + gather chain (radix sort was
 // ~8% of RF fit kernel time; reference behavior: cuML's batched node trainer
@@ -3815,6 +4124,60 @@ void kmeans_refine(torch::Tensor X, torch::Tensor C, torch::Tensor dots,
   C10_HIP_KERNEL_LAUNCH_CHECK();
 }
 
+// (labels i32 [n], sums f64 [k, d], counts f64 [k], inertia f64 [1]) of one
+// Lloyd step, as specified above kmeans_step_resident_kernel. The grid is
+// min(#64-row tiles, #CUs); the [grid, k, d] partials are reduced in f64 here.
+std::vector<torch::Tensor> kmeans_step_resident(torch::Tensor X, torch::Tensor C,
+                                                torch::Tensor x_sq) {
+  for (const torch::Tensor* t : {&X, &C, &x_sq})
+    TORCH_CHECK(t->is_cuda() && t->dtype() == torch::kFloat32 && t->is_contiguous(),
+                "kmeans_step_resident: X, C and x_sq must be contiguous f32 device tensors");
+  TORCH_CHECK(X.dim() == 2 && C.dim() == 2 && C.size(1) == X.size(1),
+              "kmeans_step_resident: X [n, d] and C [k, d] must agree in d");
+  const int64_t n = X.size(0), d = X.size(1), k = C.size(0);
+  TORCH_CHECK(x_sq.numel() == n, "kmeans_step_resident: x_sq must have one entry per row");
+  const int64_t lds = kmeans_resident_lds_bytes(k, d);
+  TORCH_CHECK(lds > 0, "kmeans_step_resident: k=", k, ", d=", d,
+              " is not legal: centres + row tile must fit ", KR_LDS_BUDGET,
+              " bytes of LDS with at most ", KR_MAX_ACC_TILES, " accumulator tiles per wave");
+  auto f64 = X.options().dtype(torch::kFloat64);
+  auto labels = torch::empty({n}, X.options().dtype(torch::kInt32));
+  if (n == 0)
+    return {labels, torch::zeros({k, d}, f64), torch::zeros({k}, f64), torch::zeros({1}, f64)};
+  int cus = 0;
+  C10_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount,
+                                      (int)X.get_device()));
+  const int64_t ntiles = (n + KR_ROWS - 1) / KR_ROWS;
+  const int64_t grid = std::min<int64_t>(ntiles, std::max(cus, 1));
+  TORCH_CHECK((ntiles + grid - 1) / grid * KR_ROWS < (1LL << 31),
+              "kmeans_step_resident: too many rows per block for the i32 counts");
+  auto part_sums = torch::empty({grid, k, d}, X.options());
+  auto part_cnt = torch::empty({grid, k}, X.options().dtype(torch::kInt32));
+  auto part_inertia = torch::empty({grid}, f64);
+  const int vec = (d % 4 == 0) && ((uintptr_t)X.data_ptr() % 16 == 0);
+  const int kt = (int)((k + 31) / 32), dw = (int)(((d + 31) / 32 + 3) / 4);
+#define KR_LAUNCH(KT_, DW_)                                                                 \
+  case (KT_) * 16 + (DW_):                                                                  \
+    hipLaunchKernelGGL((kmeans_step_resident_kernel<KT_, DW_>), dim3((unsigned)grid),       \
+                       dim3(256), (size_t)lds, cur_stream(), X.data_ptr<float>(),           \
+                       C.data_ptr<float>(), x_sq.data_ptr<float>(), n, (int)d, (int)k, vec, \
+                       labels.data_ptr<int32_t>(), part_sums.data_ptr<float>(),             \
+                       part_cnt.data_ptr<int32_t>(), part_inertia.data_ptr<double>());      \
+    break
+  switch (kt * 16 + dw) {  // every (KT, DW) the accumulator and LDS limits leave
+    KR_LAUNCH(1, 1); KR_LAUNCH(1, 2); KR_LAUNCH(1, 3); KR_LAUNCH(1, 4);
+    KR_LAUNCH(2, 1); KR_LAUNCH(2, 2); KR_LAUNCH(2, 3);
+    KR_LAUNCH(3, 1); KR_LAUNCH(3, 2); KR_LAUNCH(4, 1); KR_LAUNCH(4, 2);
+    KR_LAUNCH(5, 1); KR_LAUNCH(6, 1); KR_LAUNCH(7, 1); KR_LAUNCH(8, 1);
+    default: TORCH_CHECK(false, "kmeans_step_resident: no instantiation for k=", k, ", d=", d);
+  }
+#undef KR_LAUNCH
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return {labels, part_sums.sum({0}, false, torch::kFloat64),
+          part_cnt.sum({0}, false, torch::kFloat64),
+          part_inertia.sum({0}, true, torch::kFloat64)};
+}
+
 std::vector<torch::Tensor> rf_partition(torch::Tensor node_of_row, torch::Tensor lut,
                                         int64_t B) {
   TORCH_CHECK(node_of_row.is_cuda() && node_of_row.dtype() == torch::kInt64 &&
@@ -4385,6 +4748,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("kmeans_split_bf16_hi", &kmeans_split_bf16_hi, "centre + round f32 rows to their bf16 hi plane, with |x'|^2");
   m.def("kmeans_argmin_kn_screen", &kmeans_argmin_kn_screen, "best/second argmin over a screened [k,n] dot block; flags near-ties");
   m.def("kmeans_refine", &kmeans_refine, "exact f64 decision for the flagged rows");
+  m.def("kmeans_step_resident", &kmeans_step_resident,
+        "one-pass Lloyd step (labels, sums, counts, inertia) with the centres resident in LDS");
+  m.def("kmeans_resident_lds_bytes", &kmeans_resident_lds_bytes,
+        "dynamic LDS of kmeans_step_resident for (k, d); 0 where the shape is not legal");
   m.def("label_accumulate", &label_accumulate, "per-center sum/count scatter");
   m.def("label_accumulate_inertia", &label_accumulate_inertia, "sorted per-center sum/count + sum (x - c)^2 in the same pass",
         py::arg("X"), py::arg("labels"), py::arg("C"), py::arg("vec") = LA_VEC_DEFAULT);

@@ -10,6 +10,16 @@ decides them (`_refine_f32`) or, on request, in f64 by `kmeans_refine`
 ‖x‖²+‖c‖²−2x·c on mfma_f32_32x32x2f32 with a fused per-row argmin.
 `label_accumulate` is the vectorized per-center sum/count scatter.
 
+Small k (k < 384) with centres that fit in LDS: `kmeans_assign_reduce` runs the
+whole step in `kmeans_step_resident` (`_resident_wanted`) — one pass over X,
+the centres resident in LDS, dots and the one-hot sum accumulation both on
+mfma_f32_32x32x2f32, no [n, k] dot block in global memory, block partials
+reduced in f64 (bit-reproducible for a fixed grid). It is the default there
+(159 against 164 ms per step at 100M×128, k=200; 0.28 against 0.53 ms at
+1M×32, k=16; RESULTS.md); SRML_KMEANS_VARIANT=f32 keeps the GEMM +
+`kmeans_argmin_nk` + `label_accumulate` path, =resident asks for the kernel
+wherever it is legal. `kmeans_predict` does not use it.
+
 Across the calls of one fit X does not change, so `kmeans_assign_reduce`
 keeps the centred bf16 hi plane of X and |x'|² (`_prepared`, one entry,
 SRML_KMEANS_CACHE=0 disables it) and screens with the hi·hi term alone
@@ -54,7 +64,10 @@ def kmeans_assign_reduce(
     cache recognises X by identity, storage address, shape and torch's
     version counter: a write to X that bypasses that counter (through
     `.data`, a raw pointer, another library) is not seen.
-    SRML_KMEANS_CACHE=0 turns the cache off."""
+    SRML_KMEANS_CACHE=0 turns the cache off.
+
+    At k < 384 a contiguous f32 device X whose centres fit in LDS takes the
+    one-pass `kmeans_step_resident` kernel (`_resident_wanted`)."""
     if use_hip(X) and X.dtype == torch.float32:
         ext = hip_ops()
         if x_sq is None:
@@ -74,11 +87,66 @@ def kmeans_assign_reduce(
                     sums, counts = ext.label_accumulate(X, labels, C.shape[0])
                 return (labels, sums.to(torch.float64), counts.to(torch.float64),
                         float(inertia.item()))
+        if _resident_wanted(X, C):
+            return _step_resident(ext, X, C, x_sq)
         X = X.contiguous()
         labels, inertia = _assign(ext, X, C, x_sq)
         sums, counts = ext.label_accumulate(X, labels, C.shape[0])
         return labels, sums.to(torch.float64), counts.to(torch.float64), float(inertia.item())
     return torch_ref.kmeans_assign_reduce(X, C, x_sq)
+
+
+# `kmeans_step_resident` limits; `_resident_lds_bytes` mirrors the extension's
+# `kmeans_resident_lds_bytes(k, d)` (hip/ops.hip).
+_KR_ROWS = 64
+_KR_LDS_BUDGET = 160 * 1024
+_KR_MAX_ACC_TILES = 8
+# Whether the kernel serves the step when SRML_KMEANS_VARIANT is unset: decided
+# by the alternating timings in RESULTS.md ("KMeans resident step").
+_RESIDENT_DEFAULT = True
+
+
+def _resident_lds_bytes(k: int, d: int) -> int:
+    """LDS the resident kernel needs for (k, d); 0 where the shape is not
+    legal (accumulator tiles per wave, or centres + row tile over the LDS)."""
+    if k < 1 or d < 1:
+        return 0
+    k_pad = (k + 31) // 32 * 32
+    kt, dw = k_pad // 32, ((d + 31) // 32 + 3) // 4
+    if kt * dw > _KR_MAX_ACC_TILES:
+        return 0
+    ld = (d + 1) // 2 * 2 + 1
+    lds = (k_pad + _KR_ROWS) * ld * 4 + k_pad * 8 + _KR_ROWS * 4 + 2 * _KR_ROWS * 8
+    return lds if lds <= _KR_LDS_BUDGET else 0
+
+
+def _resident_wanted(X: torch.Tensor, C: torch.Tensor) -> bool:
+    """Route the whole step through `kmeans_step_resident`? On the GPU, for
+    contiguous f32 X, k < 384 and a (k, d) whose centres and row tile fit the
+    kernel's LDS. SRML_KMEANS_VARIANT=resident asks for the kernel, which it
+    gets wherever it is legal; =f32 and =fused keep the small-k paths they
+    name; unset, and every value that names no small-k path, follows
+    `_RESIDENT_DEFAULT`."""
+    variant = os.environ.get("SRML_KMEANS_VARIANT")
+    if variant in ("f32", "fused"):
+        return False
+    if variant != "resident" and not _RESIDENT_DEFAULT:
+        return False
+    if not (X.is_cuda and X.dtype == torch.float32 and X.dim() == 2 and X.is_contiguous()):
+        return False
+    if C.dtype != torch.float32 or X.shape[0] == 0 or C.shape[0] >= 384:
+        return False
+    return _resident_lds_bytes(C.shape[0], X.shape[1]) > 0
+
+
+def _step_resident(
+    ext, X: torch.Tensor, C: torch.Tensor, x_sq: torch.Tensor
+) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, float]:
+    """One Lloyd step in one pass over X: labels, f64 sums and counts, inertia."""
+    labels, sums, counts, inertia = ext.kmeans_step_resident(
+        X, C.contiguous(), x_sq.contiguous()
+    )
+    return labels, sums, counts, float(inertia.item())
 
 
 def kmeans_predict(X: torch.Tensor, C: torch.Tensor) -> torch.Tensor:
