@@ -2616,6 +2616,211 @@ __global__ __launch_bounds__(256) void csr_pairwise_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// knn_merge_topk_wide: the selection stage of knn_merge_topk for
+// 64 < k <= 1024. Same contract (one [nq, c] block of dots or keys consumed
+// once and folded into a per-row running top-k that survives across item
+// chunks), different selection: the 64-slot kernel serialises every insertion
+// behind a wave max-reduce, which does not scale to 1024 slots.
+//
+//  * One wave per query row, four rows per block; all state of a row is
+//    private to its wave, so the kernel has no __syncthreads. LDS ordering
+//    inside the wave is cp_wave_sync.
+//  * An entry is one u64, (ordered key << 32) | id, the cagra_search trick.
+//    Keys can be negative here (cancellation in d2, 1 - <q', i'>), so the f32
+//    bits go through the order-preserving map (all bits of a negative flipped,
+//    sign bit of a non-negative set): u64 order is (key, id) order and the
+//    smallest id wins a tie. All-ones is the empty entry.
+//  * The wave keeps a sorted list of K = pow2 >= k entries in LDS, loaded from
+//    and stored to the [nq, K] state tensor. tau = key of list[k-1] (+inf when
+//    empty); positions >= k are reset to empty after every merge.
+//  * Scan: a float4 of the row per lane, d2 < tau, survivors compacted into a
+//    512-entry LDS buffer by ballot + prefix popcount (no per-candidate loop).
+//    All list entries come from earlier columns, so the strict < is exactly
+//    the (key, id) order. NaN never passes; +inf never passes either, as in
+//    the 64-slot kernel.
+//  * Flush (buffer could not take another 256, and at the end of the block):
+//    pad to n = pow2 >= fill, bitonic-sort the n entries descending, take the
+//    element-wise min of the list's top min(n, K) positions and the buffer's
+//    min(n, K) smallest (ascending prefix of the list, then a descending run
+//    of buffer entries: bitonic), then log2(K) bitonic-merge stages.
+//  * Every loop around a barrier has a wave-uniform trip count (fill and n
+//    come from ballots); the per-lane strided loops inside hold LDS traffic
+//    only.
+//
+// LDS: 4 * (8 K + 4096) bytes per block: 48 KB at K = 1024 (three blocks per
+// CU), 20 KB at K = 128.
+//
+// Packed f32 arithmetic is switched off for this kernel and its helpers: the
+// four d2 of a lane are exactly the shape the SLP vectoriser packs. The
+// helpers carry the same attribute, or they would not inline.
+// ---------------------------------------------------------------------------
+
+#if defined(__HIP_DEVICE_COMPILE__)
+#define KW_TARGET __attribute__((target("no-packed-fp32-ops")))
+#else
+#define KW_TARGET  // the host pass knows no such feature
+#endif
+#define KW_FN __device__ __forceinline__ KW_TARGET
+
+constexpr int KW_BUF = 512;  // candidate buffer entries per wave
+constexpr unsigned long long KW_EMPTY = ~0ull;
+
+KW_FN void kw_wave_sync() {  // cp_wave_sync, under this kernel's target attribute
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+KW_FN unsigned kw_ordered(float v) {
+  const unsigned b = __builtin_bit_cast(unsigned, v);
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
+KW_FN float kw_tau(unsigned long long e) {
+  if (e == KW_EMPTY) return __builtin_inff();
+  const unsigned o = (unsigned)(e >> 32);
+  return __builtin_bit_cast(float, (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
+}
+
+// one compare-exchange of a[i], a[l]; `desc` puts the larger first
+KW_FN void kw_cmpx(unsigned long long* a, int i, int l, bool desc) {
+  const unsigned long long x = a[i], y = a[l];
+  if ((x < y) == desc) { a[i] = y; a[l] = x; }
+}
+
+// buf[0:fill) -> the K smallest of list ∪ buf, ascending, in list
+template <int K>
+KW_FN void kw_flush(unsigned long long* list, unsigned long long* buf, int fill, int k,
+                    int lane) {
+  int n = 64;  // wave-uniform: fill is
+  while (n < fill) n <<= 1;
+  for (int i = fill + lane; i < n; i += 64) buf[i] = KW_EMPTY;
+  kw_wave_sync();
+  // bitonic sort of buf[0:n), descending
+  for (int size = 2; size <= n; size <<= 1) {
+    for (int j = size >> 1; j > 0; j >>= 1) {
+      for (int t = lane; t < (n >> 1); t += 64) {
+        const int i = 2 * t - (t & (j - 1));
+        kw_cmpx(buf, i, i + j, (i & size) == 0);
+      }
+      kw_wave_sync();
+    }
+  }
+  // list's top m against buf's m smallest: m <= K, m <= n
+  const int m = n < K ? n : K;
+  for (int i = lane; i < m; i += 64) {
+    const unsigned long long b = buf[n - m + i];
+    if (b < list[K - m + i]) list[K - m + i] = b;
+  }
+  kw_wave_sync();
+  // bitonic merge of list[0:K), ascending
+  for (int j = K >> 1; j > 0; j >>= 1) {
+#pragma unroll
+    for (int t0 = 0; t0 < (K >> 1); t0 += 64) {
+      const int t = t0 + lane;
+      const int i = 2 * t - (t & (j - 1));
+      kw_cmpx(list, i, i + j, false);
+    }
+    kw_wave_sync();
+  }
+  for (int i = k + lane; i < K; i += 64) list[i] = KW_EMPTY;
+  kw_wave_sync();
+}
+
+// four columns j0 .. j0+3 of the row (and of i_sq); columns past c read as a
+// d2 above any tau
+template <bool KEYS>
+KW_FN void kw_load4(const float* g, const float* i_sq, int64_t j0, int64_t c, bool vec4,
+                    float* dot4, float* isq4) {
+  if (vec4 && j0 + 3 < c) {
+    const float4 gd = *reinterpret_cast<const float4*>(g + j0);
+    dot4[0] = gd.x; dot4[1] = gd.y; dot4[2] = gd.z; dot4[3] = gd.w;
+    if constexpr (!KEYS) {
+      const float4 gi = *reinterpret_cast<const float4*>(i_sq + j0);
+      isq4[0] = gi.x; isq4[1] = gi.y; isq4[2] = gi.z; isq4[3] = gi.w;
+    }
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const bool ok = j0 + e < c;
+      dot4[e] = ok ? g[j0 + e] : 0.0f;
+      if constexpr (!KEYS) isq4[e] = ok ? i_sq[j0 + e] : 3.0e38f;
+    }
+  }
+}
+
+template <int K, bool KEYS>
+__global__ __launch_bounds__(256) KW_TARGET void knn_merge_topk_wide_kernel(
+    const float* __restrict__ G,     // [nq, c] dot products Q @ I_chunk^T (or keys)
+    const float* __restrict__ q_sq,  // [nq]
+    const float* __restrict__ i_sq,  // [c]
+    int64_t nq, int64_t c, int64_t base, int k,
+    unsigned long long* __restrict__ state) {  // [nq, K] packed entries
+  extern __shared__ unsigned long long kw_lds[];  // [4][K + KW_BUF]
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int64_t row = (int64_t)blockIdx.x * 4 + wave;
+  // the waves of a block share no barrier below
+  if (row >= nq) return;
+
+  unsigned long long* list = kw_lds + (size_t)wave * (K + KW_BUF);
+  unsigned long long* buf = list + K;
+  unsigned long long* st = state + row * K;
+#pragma unroll
+  for (int i = 0; i < K; i += 64) list[i + lane] = st[i + lane];
+  kw_wave_sync();
+  float tau = kw_tau(list[k - 1]);
+
+  const float* g = G + row * c;
+  const float qs = KEYS ? 0.0f : q_sq[row];
+  // float4 loads need every row base 16B-aligned: c % 4 == 0
+  const bool vec4 = (c & 3) == 0;
+  // UNIFORM trip count, as in knn_merge_topk_kernel
+  const int64_t n_iter = (c + 255) / 256;
+  int fill = 0;
+  bool dirty = false;
+  float dot4[4], isq4[4], ndot4[4], nisq4[4];
+  kw_load4<KEYS>(g, i_sq, (int64_t)lane * 4, c, vec4, ndot4, nisq4);
+  for (int64_t it = 0; it < n_iter; ++it) {
+    const int64_t j0 = it * 256 + (int64_t)lane * 4;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { dot4[e] = ndot4[e]; isq4[e] = nisq4[e]; }
+    // the next iteration's loads are in flight while this one is ranked; past
+    // the last iteration every column fails j < c and nothing is read
+    kw_load4<KEYS>(g, i_sq, j0 + 256, c, vec4, ndot4, nisq4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      // + 0: -0 and +0 are one key, so that the id alone breaks their tie
+      const float d2 = (KEYS ? dot4[e] : qs + isq4[e] - 2.0f * dot4[e]) + 0.0f;
+      const bool pass = d2 < tau && j0 + e < c;
+      const unsigned long long m = __builtin_amdgcn_ballot_w64(pass);
+      const int pos = fill + (int)__builtin_amdgcn_mbcnt_hi(
+                                 (unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+      // fill <= KW_BUF - 256 here and at most 64 enter per e
+      if (pass)
+        buf[pos] = ((unsigned long long)kw_ordered(d2) << 32) | (unsigned)(base + j0 + e);
+      fill += __builtin_popcountll(m);
+    }
+    if (fill > KW_BUF - 256) {
+      kw_wave_sync();
+      kw_flush<K>(list, buf, fill, k, lane);
+      tau = kw_tau(list[k - 1]);
+      fill = 0;
+      dirty = true;
+    }
+  }
+  if (fill > 0) {
+    kw_wave_sync();
+    kw_flush<K>(list, buf, fill, k, lane);
+    dirty = true;
+  }
+  if (dirty) {
+#pragma unroll
+    for (int i = 0; i < K; i += 64) st[i + lane] = list[i + lane];
+  }
+}
+
+// ---------------------------------------------------------------------------
 // gather_dists: d2[i][j] = ||A[i] - B[cand[i][j]]||^2 — the nn-descent /
 // beam-search hot op (per-row private candidate lists make this a gathered
 // row-vs-rows reduction, not a GEMM). One wave per output row: A[i] is
@@ -4263,6 +4468,55 @@ void knn_merge_topk_keys(torch::Tensor G, int64_t base, torch::Tensor best_d,
   C10_HIP_KERNEL_LAUNCH_CHECK();
 }
 
+static inline int64_t kw_slots(int64_t k) {  // pow2 >= k in {128, ..., 1024}
+  int64_t K = 128;
+  while (K < k) K <<= 1;
+  return K;
+}
+
+template <bool KEYS>
+static void knn_merge_topk_wide_impl(torch::Tensor G, const float* q_sq, const float* i_sq,
+                                     int64_t base, torch::Tensor state, int64_t k) {
+  TORCH_CHECK(G.is_cuda() && G.dtype() == torch::kFloat32 && G.is_contiguous() && G.dim() == 2);
+  TORCH_CHECK(state.is_cuda() && state.dtype() == torch::kInt64 && state.dim() == 2 &&
+              state.is_contiguous());
+  TORCH_CHECK(k > 64 && k <= 1024, "knn_merge_topk_wide serves 64 < k <= 1024, got ", k);
+  const int64_t K = kw_slots(k);
+  const int64_t nq = G.size(0);
+  const int64_t c = G.size(1);
+  TORCH_CHECK(state.size(0) == nq && state.size(1) == K, "state must be [nq, ", K, "]");
+  TORCH_CHECK(base >= 0 && base + c < ((int64_t)1 << 31), "item ids must stay below 2^31");
+  if (nq == 0 || c == 0) return;
+  const dim3 grid((unsigned)((nq + 3) / 4));
+  const size_t lds = 4 * (size_t)(K + KW_BUF) * sizeof(unsigned long long);
+  auto* st = reinterpret_cast<unsigned long long*>(state.data_ptr<int64_t>());
+#define KW_LAUNCH(KK)                                                                         \
+  hipLaunchKernelGGL((knn_merge_topk_wide_kernel<KK, KEYS>), grid, dim3(256), lds,            \
+                     cur_stream(), G.data_ptr<float>(), q_sq, i_sq, nq, c, base, (int)k, st)
+  switch (K) {
+    case 128: KW_LAUNCH(128); break;
+    case 256: KW_LAUNCH(256); break;
+    case 512: KW_LAUNCH(512); break;
+    default: KW_LAUNCH(1024); break;
+  }
+#undef KW_LAUNCH
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+}
+
+void knn_merge_topk_wide(torch::Tensor G, torch::Tensor q_sq, torch::Tensor i_sq,
+                         int64_t base, torch::Tensor state, int64_t k) {
+  TORCH_CHECK(q_sq.is_cuda() && q_sq.dtype() == torch::kFloat32 && q_sq.is_contiguous());
+  TORCH_CHECK(i_sq.is_cuda() && i_sq.dtype() == torch::kFloat32 && i_sq.is_contiguous());
+  TORCH_CHECK(G.dim() == 2 && q_sq.dim() == 1 && i_sq.dim() == 1);
+  TORCH_CHECK(q_sq.size(0) == G.size(0) && i_sq.size(0) == G.size(1));
+  knn_merge_topk_wide_impl<false>(G, q_sq.data_ptr<float>(), i_sq.data_ptr<float>(), base,
+                                  state, k);
+}
+
+void knn_merge_topk_wide_keys(torch::Tensor G, int64_t base, torch::Tensor state, int64_t k) {
+  knn_merge_topk_wide_impl<true>(G, nullptr, nullptr, base, state, k);
+}
+
 template <int OP>
 static void pairwise_dist_launch(unsigned grid, const float* Q, const float* I, int64_t nq,
                                  int64_t c, int d, float p, int64_t n_it, float* out) {
@@ -4766,6 +5020,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rf_partition", &rf_partition, "counting-sort rows by node -> (perm, seg_off)");
   m.def("rf_reroute", &rf_reroute, "one-pass row-to-child reassignment");
   m.def("knn_merge_topk", &knn_merge_topk, "running top-k merge over a GEMM dot block");
+  m.def("knn_merge_topk_wide", &knn_merge_topk_wide,
+        "running top-k merge over a GEMM dot block, 64 < k <= 1024");
+  m.def("knn_merge_topk_wide_keys", &knn_merge_topk_wide_keys,
+        "running top-k merge over a block of distance keys, 64 < k <= 1024");
   m.def("knn_merge_topk_keys", &knn_merge_topk_keys,
         "running top-k merge over a block of distance keys");
   m.def("pairwise_dist", &pairwise_dist,

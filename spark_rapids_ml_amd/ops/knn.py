@@ -4,7 +4,9 @@ HIP path (gfx950): `knn_select` streams 128-item tiles against 64-query
 blocks, fusing the ||q-i||^2 expansion (MFMA) with per-query top-k candidate
 pools held in LDS — the [nq, ni] distance matrix is never materialized
 (reference NearestNeighborsMG tiled distance + top-k).
-Falls back to the chunked torch path for k > 64 or CPU.
+The default path is library GEMM + the `knn_merge_topk` selection kernel for
+k <= 64 and its sorted-list sibling `knn_merge_topk_wide` for 64 < k <= 1024;
+k > 1024 and CPU tensors take the chunked torch path.
 
 `knn_topk_metric` serves the metrics other than euclidean (UMAP's `metric`):
 dot-product metrics on preprocessed rows through the same GEMM + selection
@@ -33,9 +35,11 @@ def knn_topk(Q: torch.Tensor, I: torch.Tensor, k: int) -> Tuple[torch.Tensor, to
     running per-query top-k — the [q, chunk] distance matrix is never
     materialized and each GEMM output byte is read exactly once (the old
     torch path wrote d2, re-read it with multi-pass torch.topk and merged
-    chunks with cat+topk+gather). SRML_KNN_KERNEL=1 keeps the all-in-one
-    MFMA knn_select kernel (measured slower at 1M items; profiles/README.md),
-    SRML_KNN_KERNEL=0 forces the torch reference path."""
+    chunks with cat+topk+gather). 64 < k <= 1024 runs the same GEMM into
+    `knn_merge_topk_wide`; k > 1024 takes the torch path. SRML_KNN_KERNEL=1
+    keeps the all-in-one MFMA knn_select kernel for k <= 64 (measured slower
+    at 1M items; profiles/README.md), SRML_KNN_KERNEL=0 forces the torch
+    reference path."""
     import os
 
     mode = os.environ.get("SRML_KNN_KERNEL", "")
@@ -48,13 +52,71 @@ def knn_topk(Q: torch.Tensor, I: torch.Tensor, k: int) -> Tuple[torch.Tensor, to
         mode != "0"
         and use_hip(Q, I)
         and k_eff == k
-        and k <= 64
+        and _kernel_serves(k, I.shape[0])
         and Q.dtype == torch.float32
         and I.dtype == torch.float32
         and Q.shape[0] > 0
     ):
         return _knn_topk_gemm_select(Q.contiguous(), I.contiguous(), k)
     return torch_ref.knn_topk(Q, I, k)
+
+
+# `knn_merge_topk_wide`: 64 < k <= WIDE_K_MAX, K = pow2 >= k list slots per row
+WIDE_K_MAX = 1024
+# The wide kernel reads and writes its [nq, K] u64 state once per chunk call,
+# 16 K bytes per row against 4 ichunk bytes of block. Queries are therefore
+# tiled so that an item chunk is WIDE_CHUNK_FACTOR * K columns wide where ni
+# allows (chunk_elems // (factor * K) rows per tile).
+# Timed once on an MI355X (tools/time_knn_wide.py --cases many --factors
+# 8,16,32: 1M queries x 100k items x 64, seconds per call, spread < 0.5 %):
+#   factor      8      16      32
+#   k = 128   0.306   0.270   0.258
+#   k = 1024  0.527   0.525   0.535
+# 8 loses at small K, 32 at large K (its 16 384-row tiles shorten the GEMM);
+# 16 is within 5 % of the best at both ends.
+WIDE_CHUNK_FACTOR = 16
+
+
+def _kernel_serves(k: int, ni: int) -> bool:
+    """k <= 64 in the 64-slot kernel; up to WIDE_K_MAX in the wide one, whose
+    packed entries hold item ids below 2^31."""
+    return k <= 64 or (k <= WIDE_K_MAX and ni < 1 << 31)
+
+
+def _wide_slots(k: int) -> int:
+    return max(128, 1 << (k - 1).bit_length())
+
+
+def _wide_unpack(state: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(f32 keys, int64 ids) of the first k packed entries per row:
+    (ordered key << 32) | id, -1 = empty (key +inf, id -1)."""
+    s = state[:, :k]
+    o = (s >> 32) & 0xFFFFFFFF
+    # inverse of the order-preserving map: sign bit set = non-negative
+    bits = torch.where(o >= 1 << 31, o - (1 << 31), 0xFFFFFFFF - o)
+    bits = torch.where(bits >= 1 << 31, bits - (1 << 32), bits).to(torch.int32)
+    empty = s == -1
+    keys = bits.view(torch.float32).masked_fill(empty, float("inf"))
+    return keys, (s & 0xFFFFFFFF).masked_fill(empty, -1)
+
+
+def _query_tiled(
+    nq: int,
+    ni: int,
+    k: int,
+    chunk_elems: int,
+    select_rows: Callable[[int, int], Tuple[torch.Tensor, torch.Tensor]],
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`select_rows(qs, qe)` over all queries at once for k <= 64, over query
+    tiles sized for the wide kernel's state traffic above."""
+    if k <= 64:
+        return select_rows(0, nq)
+    width = max(256, min(ni, WIDE_CHUNK_FACTOR * _wide_slots(k)))
+    qtile = max(4, chunk_elems // width)
+    tiles = [select_rows(qs, min(nq, qs + qtile)) for qs in range(0, nq, qtile)]
+    if len(tiles) == 1:
+        return tiles[0]
+    return torch.cat([t[0] for t in tiles]), torch.cat([t[1] for t in tiles])
 
 
 def _chunked_select(
@@ -68,13 +130,12 @@ def _chunked_select(
     """Running 64-slot top-k over item chunks: `merge_chunk(Gv, s, e, best_d,
     best_i)` fills the [nq, e-s] scratch block Gv for items s:e and merges it
     into the slots. Returns the k smallest keys per row, ascending, and their
-    item indices."""
-    # 64 candidate slots per query; lanes >= k carry a -inf sentinel so they
-    # never own tau (the running worst kept distance) inside the kernel
-    best_d = torch.full((nq, 64), float("inf"), dtype=torch.float32, device=dev)
-    if k < 64:
-        best_d[:, k:] = float("-inf")
-    best_i = torch.full((nq, 64), -1, dtype=torch.int64, device=dev)
+    item indices. For k > 64 `best_d` is the packed [nq, K] int64 state of the
+    wide kernel and `best_i` is None."""
+    if k > 64:
+        best_d, best_i = torch.full((nq, _wide_slots(k)), -1, dtype=torch.int64, device=dev), None
+    else:
+        best_d, best_i = _slot_buffers(nq, k, dev)
 
     # multiple of 64 so every non-final chunk keeps the kernel's float4 path
     # (row base 16B-aligned requires chunk width % 4 == 0)
@@ -88,11 +149,23 @@ def _chunked_select(
         )
         merge_chunk(Gv, s, e, best_d, best_i)
 
+    if k > 64:
+        return _wide_unpack(best_d, k)
     if k < 64:
         best_d[:, k:] = float("inf")  # dead slots sort last
     d_sorted, order = torch.sort(best_d, dim=1)
     i_sorted = best_i.gather(1, order)
     return d_sorted[:, :k], i_sorted[:, :k].contiguous()
+
+
+def _slot_buffers(nq: int, k: int, dev: torch.device) -> Tuple[torch.Tensor, torch.Tensor]:
+    # 64 candidate slots per query; lanes >= k carry a -inf sentinel so they
+    # never own tau (the running worst kept distance) inside the kernel
+    best_d = torch.full((nq, 64), float("inf"), dtype=torch.float32, device=dev)
+    if k < 64:
+        best_d[:, k:] = float("-inf")
+    best_i = torch.full((nq, 64), -1, dtype=torch.int64, device=dev)
+    return best_d, best_i
 
 
 def _gemm_select_keys(
@@ -104,14 +177,24 @@ def _gemm_select_keys(
     chunk_elems: int,
 ) -> Tuple[torch.Tensor, torch.Tensor]:
     """k smallest q_sq[r] + i_sq[j] - 2 <Q[r], I[j]> per row: library GEMM for
-    the dot block + the own `knn_merge_topk` selection kernel."""
+    the dot block + the own `knn_merge_topk` selection kernel
+    (`knn_merge_topk_wide` for k > 64)."""
     ext = hip_ops()
+    ni = I.shape[0]
 
-    def merge_chunk(Gv, s, e, best_d, best_i):
-        torch.mm(Q, I[s:e].T, out=Gv)
-        ext.knn_merge_topk(Gv, q_sq, i_sq[s:e].contiguous(), s, best_d, best_i)
+    def select_rows(qs, qe):
+        Qt, qt_sq = Q[qs:qe], q_sq[qs:qe]
 
-    return _chunked_select(Q.shape[0], I.shape[0], k, Q.device, chunk_elems, merge_chunk)
+        def merge_chunk(Gv, s, e, best_d, best_i):
+            torch.mm(Qt, I[s:e].T, out=Gv)
+            if k > 64:
+                ext.knn_merge_topk_wide(Gv, qt_sq, i_sq[s:e], s, best_d, k)
+            else:
+                ext.knn_merge_topk(Gv, qt_sq, i_sq[s:e].contiguous(), s, best_d, best_i)
+
+        return _chunked_select(qe - qs, ni, k, Q.device, chunk_elems, merge_chunk)
+
+    return _query_tiled(Q.shape[0], ni, k, chunk_elems, select_rows)
 
 
 def _knn_topk_gemm_select(
@@ -197,14 +280,16 @@ def knn_topk_metric(
     library GEMM + `knn_merge_topk`; the tile family (manhattan, chebyshev,
     minkowski, canberra, hamming) runs the `pairwise_dist` kernel per item
     chunk + `knn_merge_topk_keys`, the root / division by d applied to the k
-    survivors only. CPU tensors, k > 64 and non-f32 input take the chunked
-    torch path."""
+    survivors only; 64 < k <= 1024 swaps in the `knn_merge_topk_wide` pair of
+    selection kernels. CPU tensors, k > 1024 and non-f32 input take the
+    chunked torch path."""
     metric, p = resolve_metric(metric, p)
     if metric == "euclidean":
         return knn_topk(Q, I, k)
     kernel_path = (
         use_hip(Q, I)
-        and k <= min(64, I.shape[0])
+        and k <= I.shape[0]
+        and _kernel_serves(k, I.shape[0])
         and Q.dtype == torch.float32
         and I.dtype == torch.float32
         and Q.shape[0] > 0
@@ -236,12 +321,21 @@ def _tile_select_keys(
 ) -> Tuple[torch.Tensor, torch.Tensor]:
     """k smallest `pairwise_dist` keys per row, chunked as the GEMM path is."""
     ext = hip_ops()
+    ni = I.shape[0]
 
-    def merge_chunk(Gv, s, e, best_d, best_i):
-        ext.pairwise_dist(Q, I[s:e], op, float(p), Gv)
-        ext.knn_merge_topk_keys(Gv, s, best_d, best_i)
+    def select_rows(qs, qe):
+        Qt = Q[qs:qe]
 
-    return _chunked_select(Q.shape[0], I.shape[0], k, Q.device, chunk_elems, merge_chunk)
+        def merge_chunk(Gv, s, e, best_d, best_i):
+            ext.pairwise_dist(Qt, I[s:e], op, float(p), Gv)
+            if k > 64:
+                ext.knn_merge_topk_wide_keys(Gv, s, best_d, k)
+            else:
+                ext.knn_merge_topk_keys(Gv, s, best_d, best_i)
+
+        return _chunked_select(qe - qs, ni, k, Q.device, chunk_elems, merge_chunk)
+
+    return _query_tiled(Q.shape[0], ni, k, chunk_elems, select_rows)
 
 
 # ---------------------------------------------------------------------------
@@ -331,8 +425,9 @@ def knn_topk_metric_sparse(
     `knn_merge_topk_keys` folds into the running top-k; only stored entries
     are ever touched. The block never exceeds `chunk_elems` elements (2 GB by
     default, as on the dense path): queries are taken in tiles of
-    chunk_elems // chunk rows, each against every item chunk. CPU devices
-    and k > 64 take the torch path, which densifies bounded row chunks."""
+    chunk_elems // chunk rows, each against every item chunk. 64 < k <= 1024
+    folds with `knn_merge_topk_wide_keys`. CPU devices and k > 1024 take the
+    torch path, which densifies bounded row chunks."""
     metric, p = resolve_metric(metric, p, sparse=True)
     if Q.shape[1] != I.shape[1]:
         raise ValueError(f"queries have {Q.shape[1]} columns, items {I.shape[1]}")
@@ -346,7 +441,8 @@ def knn_topk_metric_sparse(
     kernel_path = (
         dev.type == "cuda"
         and use_hip(torch.empty(0, device=dev))
-        and k <= min(64, ni)
+        and k <= ni
+        and _kernel_serves(k, ni)
         and nq > 0
     )
     if not kernel_path:
@@ -397,12 +493,17 @@ def knn_topk_metric_sparse(
                 t_ptr, q_col, q_val, colptr, c_row, c_val, t_A, B[s:e].contiguous(),
                 op, float(p), Gv,
             )
-            ext.knn_merge_topk_keys(Gv, s, best_d, best_i)
+            if k > 64:
+                ext.knn_merge_topk_wide_keys(Gv, s, best_d, k)
+            else:
+                ext.knn_merge_topk_keys(Gv, s, best_d, best_i)
 
         return _chunked_select(qe - qs, ni, k, dev, chunk * (qe - qs), merge_chunk)
 
     # one tile unless nq * chunk passes the budget (65 536 rows at 8192 items);
-    # beyond it each tile rebuilds the chunk CSCs, a sort of nnz per tile
+    # beyond it each tile rebuilds the chunk CSCs, a sort of nnz per tile. The
+    # same for k > 64: `chunk` is capped by csr_pairwise's LDS accumulator,
+    # so smaller tiles could not widen the item chunk for the wide kernel
     qtile = max(4, chunk_elems // chunk)
     tiles = [select_tile(qs, min(nq, qs + qtile)) for qs in range(0, nq, qtile)]
     keys = torch.cat([t[0] for t in tiles]) if len(tiles) > 1 else tiles[0][0]

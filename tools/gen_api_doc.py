@@ -121,7 +121,7 @@ Any other DBSCAN metric raises `ValueError` at `transform`.
 
 Under `build_algo="auto"` the per-coordinate metrics and hellinger build the graph by brute force at any size; the L2-reducible ones switch to nn-descent above 50 000 rows as euclidean does. An unknown name raises and lists the accepted names.
 
-Sparse input. A scipy CSR feature column stays CSR (`enable_sparse_data_optim`: `None` follows the input, `True` requires CSR, `False` densifies as before). The graph is then built by `ops/knn.py::knn_topk_metric_sparse`: per item chunk a CSC is built in torch and the `csr_pairwise` HIP kernel walks only the stored entries of both sides, `knn_merge_topk_keys` keeps the running top-k. Every metric above except `chebyshev`/`linf` and `correlation` is accepted, plus `jaccard`; those two and `build_algo="nn_descent"` raise a `ValueError` naming "sparse input" (`auto` means brute force). `UMAPModel.rawData` is then a `scipy.sparse.csr_matrix`, persisted as its three arrays and shape; `transform` takes a CSR batch as is and converts a dense one.
+Sparse input. A scipy CSR feature column stays CSR (`enable_sparse_data_optim`: `None` follows the input, `True` requires CSR, `False` densifies as before). The graph is then built by `ops/knn.py::knn_topk_metric_sparse`: per item chunk a CSC is built in torch and the `csr_pairwise` HIP kernel walks only the stored entries of both sides, `knn_merge_topk_keys` keeps the running top-k. On all three brute-force paths (dense GEMM metrics, dense tile metrics, sparse) `n_neighbors + 1` ≤ 64 selects in the 64-slot kernel and up to 1024 in `knn_merge_topk_wide`; only above 1024 does the selection take the torch path. Every metric above except `chebyshev`/`linf` and `correlation` is accepted, plus `jaccard`; those two and `build_algo="nn_descent"` raise a `ValueError` naming "sparse input" (`auto` means brute force). `UMAPModel.rawData` is then a `scipy.sparse.csr_matrix`, persisted as its three arrays and shape; `transform` takes a CSR batch as is and converts a dense one.
 
 ## Evaluators
 
