@@ -3627,6 +3627,291 @@ __global__ __launch_bounds__(64) void cagra_prune_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// nn_descent_join: one nn-descent round (the local join) for every node in one
+// launch. Node i's candidates are G[i] ∪ ⋃_t G[join[i][t]] ∪ rev[i] without i,
+// each id once; G'[i] is the deg of them nearest to X[i], ascending by
+// (key, id), Gd'[i] their squared-L2 keys; a row with fewer than deg distinct
+// candidates ends in (i, 3.4e38) fillers. The torch round gathers an
+// [n, J*deg + R] id block, keys every entry of it and sorts; here the block
+// never exists and a row of X is read only for an id that can still matter.
+//
+//  * One wave per node, four nodes per block (gather_dists). X[i] sits in
+//    registers, NSEG elements per lane.
+//  * The running list is SLOTS entries per lane (slot s*64+lane, live below
+//    deg), each packed as ordered-key bits << 32 | id, so one u64 compare
+//    orders by key and then id, and tau is the wave max of the live entries
+//    (knn_merge_topk's tau with the tie rule built in). Live slots start as
+//    the filler, so a short row needs no fix-up. The ids of the list are
+//    mirrored in LDS (lid) for the membership scan below.
+//  * G[i] enters first through the same insert with its keys from Gd.
+//  * Candidates are read 64 at a time, one per lane, in the order of the
+//    torch round's block: lane q takes G[join[i][q / deg]][q % deg], the tail
+//    lanes take rev. A join id that is i itself or repeats an earlier join id
+//    is dropped whole (i's own row is already in).
+//  * A lane drops its id when it is i, when it is in the list (scan of lid,
+//    exact), or when the per-wave filter holds it. The filter is a
+//    direct-mapped table of ids already keyed for this node: such an id is
+//    in the list or lost to a tau that has only shrunk since. It compares
+//    whole ids, so a collision forgets an id and never invents one. Claiming
+//    a filter slot with (id, lane) and reading it back also leaves one lane
+//    per id among the repeats inside a batch.
+//  * Survivors are compacted by ballot into a queue; ROWS * TEAMS of them
+//    have their rows in flight before the butterflies (ivf_scan_topk's ROWS).
+//    With d <= 32 the wave splits into four 16-lane teams (TL = 16, two
+//    elements per lane), one survivor each.
+//  * The insert re-tests membership on the registers, so the result does not
+//    depend on the filter: an id enters at most once.
+//  * At the end the list is ranked through LDS (the filter's memory) and
+//    written in ascending order.
+// Ids are i32 inside (n < 2^31); G, join and rev are read as i64 and an id
+// outside [0, n) is dropped, never dereferenced. Packed f32 is off as for the
+// wide top-k kernel, and lanes are read with the ds_bpermute / readlane
+// builtins for the reason given there.
+// LDS per block: 4 * (4096 + 256 * SLOTS + 256) bytes, 21 KB at SLOTS = 4.
+// Reference: cuVS nn_descent local join (umap.py:359-378).
+// ---------------------------------------------------------------------------
+
+constexpr int NJ_MAX_DEG = 256;
+constexpr int NJ_MAX_JOIN = 64;  // join ids are held one per lane
+constexpr int NJ_TAB = 512;      // filter entries per wave
+constexpr unsigned long long NJ_DEAD = 0x00000000ffffffffull;  // below any entry, id -1
+constexpr float NJ_FILL_KEY = 3.4e38f;
+typedef int nj_int4 __attribute__((ext_vector_type(4)));
+
+KW_FN int nj_lane(int v, int src) { return __builtin_amdgcn_ds_bpermute(src << 2, v); }
+
+KW_FN float nj_lane(float v, int src) {
+  return __builtin_bit_cast(float, nj_lane(__builtin_bit_cast(int, v), src));
+}
+
+KW_FN unsigned long long nj_pack(float key, int id) {
+  return ((unsigned long long)kw_ordered(key + 0.0f) << 32) | (unsigned)id;
+}
+
+KW_FN float nj_key(unsigned long long e) {
+  const unsigned o = (unsigned)(e >> 32);
+  return __builtin_bit_cast(float, (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
+}
+
+template <int SLOTS>
+KW_FN unsigned long long nj_wave_max(const unsigned long long (&cur)[SLOTS], int lane) {
+  unsigned long long v = cur[0];
+#pragma unroll
+  for (int s = 1; s < SLOTS; ++s) v = cur[s] > v ? cur[s] : v;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const unsigned lo = (unsigned)nj_lane((int)(unsigned)v, lane ^ off);
+    const unsigned hi = (unsigned)nj_lane((int)(unsigned)(v >> 32), lane ^ off);
+    const unsigned long long o = ((unsigned long long)hi << 32) | lo;
+    v = o > v ? o : v;
+  }
+  return v;
+}
+
+// The lanes with `valid` offer entry e; every lane of the wave must call it.
+// An offered id that the list holds is skipped, so an id enters once.
+template <int SLOTS>
+KW_FN void nj_insert(unsigned long long e, bool valid, unsigned long long (&cur)[SLOTS],
+                     unsigned long long& tau, int* lid, int lane) {
+  unsigned long long m = __builtin_amdgcn_ballot_w64(valid && e < tau);
+  while (m) {
+    const int src = __builtin_ctzll(m);
+    m &= m - 1;
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)e, src);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(e >> 32), src);
+    const unsigned long long v = ((unsigned long long)hi << 32) | lo;
+    if (v >= tau) continue;  // tau shrank since the ballot
+    bool has = false;
+    unsigned long long lmax = cur[0];
+#pragma unroll
+    for (int s = 0; s < SLOTS; ++s) {
+      has |= (unsigned)cur[s] == lo;
+      lmax = cur[s] > lmax ? cur[s] : lmax;
+    }
+    if (__builtin_amdgcn_ballot_w64(has)) continue;
+    // evict the current worst slot
+    const unsigned long long owners = __builtin_amdgcn_ballot_w64(lmax == tau);
+    if (lane == __builtin_ctzll(owners)) {
+      bool done = false;
+#pragma unroll
+      for (int s = 0; s < SLOTS; ++s) {
+        if (!done && cur[s] == tau) {
+          cur[s] = v;
+          lid[s * 64 + lane] = (int)lo;
+          done = true;
+        }
+      }
+    }
+    tau = nj_wave_max<SLOTS>(cur, lane);
+  }
+}
+
+template <int SLOTS, int NSEG, int TL>  // TL lanes per team, d <= NSEG * TL
+__global__ __launch_bounds__(256) KW_TARGET void nn_descent_join_kernel(
+    const float* __restrict__ X,       // [n, d]
+    const int64_t* __restrict__ G,     // [n, deg]
+    const float* __restrict__ Gd,      // [n, deg]
+    const int64_t* __restrict__ join,  // [n, J]
+    const int64_t* __restrict__ rev,   // [n, R]
+    int64_t n, int d, int deg, int J, int R,
+    int64_t* __restrict__ G_out,       // [n, deg]
+    float* __restrict__ Gd_out,        // [n, deg]
+    int* __restrict__ stats) {         // [n] rows keyed, or null
+  constexpr int TEAMS = 64 / TL;
+  constexpr int ROWS = NSEG <= 4 ? 4 : (NSEG <= 8 ? 2 : 1);
+  __shared__ unsigned long long nj_tab[4][NJ_TAB];
+  __shared__ __attribute__((aligned(16))) int nj_lid[4][64 * SLOTS];
+  __shared__ int nj_q[4][64];
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int64_t node = (int64_t)blockIdx.x * 4 + wave;
+  // the waves of a block share no barrier below
+  if (node >= n) return;
+  const int tl = lane & (TL - 1);
+  const int team = lane / TL;
+  unsigned long long* tab = nj_tab[wave];
+  int* lid = nj_lid[wave];
+  int* queue = nj_q[wave];
+
+  float a_reg[NSEG];
+  const float* arow = X + node * d;
+#pragma unroll
+  for (int s = 0; s < NSEG; ++s) {
+    const int idx = s * TL + tl;
+    a_reg[s] = (idx < d) ? arow[idx] : 0.0f;
+  }
+
+#pragma unroll
+  for (int i = 0; i < NJ_TAB; i += 64) tab[i + lane] = ~0ull;
+  const unsigned long long fill = nj_pack(NJ_FILL_KEY, (int)node);
+  unsigned long long cur[SLOTS];
+#pragma unroll
+  for (int s = 0; s < SLOTS; ++s) {
+    const bool live = s * 64 + lane < deg;
+    cur[s] = live ? fill : NJ_DEAD;
+    lid[s * 64 + lane] = live ? (int)node : -1;
+  }
+  unsigned long long tau = fill;
+
+  // the node's own list, with the keys it already has
+#pragma unroll
+  for (int s = 0; s < SLOTS; ++s) {
+    const int slot = s * 64 + lane;
+    const int64_t g = slot < deg ? G[node * deg + slot] : -1;
+    const bool ok = g >= 0 && g < n && g != node;
+    const float key = ok ? Gd[node * deg + slot] : 0.0f;
+    nj_insert<SLOTS>(nj_pack(key, (int)g), ok, cur, tau, lid, lane);
+  }
+
+  // join ids, one per lane; the node itself and repeats are dropped
+  const int64_t jv = lane < J ? join[node * J + lane] : -1;
+  int jn = (jv >= 0 && jv < n && jv != node) ? (int)jv : -1;
+  for (int t = 0; t + 1 < J; ++t) {
+    const int v = __builtin_amdgcn_readlane(jn, t);
+    if (lane > t && v == jn) jn = -1;
+  }
+
+  const int n_g = J * deg, n_c = n_g + R;
+  const int n_l4 = (deg + 3) >> 2;
+  int keyed = 0;
+  for (int c0 = 0; c0 < n_c; c0 += 64) {
+    const int q = c0 + lane;
+    const int t = q < n_g ? q / deg : 0;
+    const int jid = nj_lane(jn, t);
+    int64_t cv = -1;
+    if (q < n_g) {
+      if (jid >= 0) cv = G[(int64_t)jid * deg + (q - t * deg)];
+    } else if (q < n_c) {
+      cv = rev[node * R + (q - n_g)];
+    }
+    bool ok = cv >= 0 && cv < n && cv != node;
+    const int c = ok ? (int)cv : -1;
+    const unsigned h = ((unsigned)c * 0x9E3779B1u) >> 23;  // NJ_TAB = 2^9
+    kw_wave_sync();  // lid, tab and queue as the last batch left them
+    if (ok && (int)(tab[h] >> 32) == c) ok = false;
+    if (__builtin_amdgcn_ballot_w64(ok)) {
+      const nj_int4* l4 = reinterpret_cast<const nj_int4*>(lid);
+      bool hit = false;
+      for (int i = 0; i < n_l4; ++i) {
+        const nj_int4 v = l4[i];  // one address per wave: a broadcast read
+        hit |= v.x == c || v.y == c || v.z == c || v.w == c;
+      }
+      ok = ok && !hit;
+    }
+    // claim the filter slot; of the lanes of this batch with one id, the one
+    // that reads itself back keeps it
+    if (ok) tab[h] = ((unsigned long long)(unsigned)c << 32) | (unsigned)lane;
+    kw_wave_sync();
+    if (ok) {
+      const unsigned long long e = tab[h];
+      if ((int)(e >> 32) == c && (int)(unsigned)e != lane) ok = false;
+    }
+    const unsigned long long m = __builtin_amdgcn_ballot_w64(ok);
+    const int pos = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32),
+                                                   __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+    if (ok) queue[pos] = c;
+    kw_wave_sync();
+    const int cnt = __builtin_popcountll(m);
+    keyed += cnt;
+
+    for (int r0 = 0; r0 < cnt; r0 += ROWS * TEAMS) {
+      int cid[ROWS];
+      float acc[ROWS];
+#pragma unroll
+      for (int u = 0; u < ROWS; ++u) {
+        const int r = r0 + u * TEAMS + team;
+        cid[u] = r < cnt ? queue[r] : -1;
+        if constexpr (TEAMS == 1) cid[u] = __builtin_amdgcn_readfirstlane(cid[u]);
+        acc[u] = 0.0f;
+        if (cid[u] >= 0) {
+          const float* xrow = X + (int64_t)cid[u] * d;
+#pragma unroll
+          for (int s = 0; s < NSEG; ++s) {
+            const int idx = s * TL + tl;
+            const float xv = (idx < d) ? xrow[idx] : 0.0f;
+            const float diff = a_reg[s] - xv;
+            acc[u] = __builtin_fmaf(diff, diff, acc[u]);
+          }
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < ROWS; ++u) {
+#pragma unroll
+        for (int off = TL / 2; off > 0; off >>= 1) acc[u] += nj_lane(acc[u], lane ^ off);
+      }
+#pragma unroll
+      for (int u = 0; u < ROWS; ++u)
+        nj_insert<SLOTS>(nj_pack(acc[u], cid[u]), tl == 0 && cid[u] >= 0, cur, tau, lid, lane);
+    }
+  }
+
+  // rank the list through LDS: entries are distinct but for the fillers,
+  // which the slot number orders
+  kw_wave_sync();
+#pragma unroll
+  for (int s = 0; s < SLOTS; ++s)
+    if (s * 64 + lane < deg) tab[s * 64 + lane] = cur[s];
+  kw_wave_sync();
+  int rank[SLOTS];
+#pragma unroll
+  for (int s = 0; s < SLOTS; ++s) rank[s] = 0;
+  for (int t = 0; t < deg; ++t) {
+    const unsigned long long b = tab[t];
+#pragma unroll
+    for (int s = 0; s < SLOTS; ++s)
+      rank[s] += (b < cur[s] || (b == cur[s] && t < s * 64 + lane)) ? 1 : 0;
+  }
+#pragma unroll
+  for (int s = 0; s < SLOTS; ++s) {
+    if (s * 64 + lane < deg) {
+      G_out[node * deg + rank[s]] = (int64_t)(unsigned)cur[s];
+      Gd_out[node * deg + rank[s]] = nj_key(cur[s]);
+    }
+  }
+  if (stats != nullptr && lane == 0) stats[node] = keyed;
+}
+
+// ---------------------------------------------------------------------------
 // CSR GLM kernels (the reference's LogisticRegressionMG sparse path,
 // classification.py:960-966, runs cuML SpMM; torch/rocSPARSE here spent its
 // time in f64 index_add column stats, a 400M-pair radix-sort transpose and
@@ -4890,6 +5175,87 @@ std::vector<torch::Tensor> cagra_prune(torch::Tensor G, int64_t D_out) {
   return {P, detour};
 }
 
+static inline bool nj_overlap(const torch::Tensor& a, const torch::Tensor& b) {
+  const char* a0 = static_cast<const char*>(a.data_ptr());
+  const char* b0 = static_cast<const char*>(b.data_ptr());
+  return a0 < b0 + b.nbytes() && b0 < a0 + a.nbytes();
+}
+
+template <int SLOTS, int NSEG, int TL>
+static void nn_descent_join_launch(unsigned grid, const float* X, const int64_t* G,
+                                   const float* Gd, const int64_t* join, const int64_t* rev,
+                                   int64_t n, int d, int deg, int J, int R, int64_t* G_out,
+                                   float* Gd_out, int* stats) {
+  hipLaunchKernelGGL((nn_descent_join_kernel<SLOTS, NSEG, TL>), dim3(grid), dim3(256), 0,
+                     cur_stream(), X, G, Gd, join, rev, n, d, deg, J, R, G_out, Gd_out, stats);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+}
+
+template <int SLOTS>
+static void nn_descent_join_slots(unsigned grid, const float* X, const int64_t* G,
+                                  const float* Gd, const int64_t* join, const int64_t* rev,
+                                  int64_t n, int d, int deg, int J, int R, int64_t* G_out,
+                                  float* Gd_out, int* stats) {
+#define NJ_ARGS grid, X, G, Gd, join, rev, n, d, deg, J, R, G_out, Gd_out, stats
+  if (d <= 32) nn_descent_join_launch<SLOTS, 2, 16>(NJ_ARGS);  // four teams per wave
+  else if (d <= 128) nn_descent_join_launch<SLOTS, 2, 64>(NJ_ARGS);
+  else if (d <= 256) nn_descent_join_launch<SLOTS, 4, 64>(NJ_ARGS);
+  else if (d <= 512) nn_descent_join_launch<SLOTS, 8, 64>(NJ_ARGS);
+  else nn_descent_join_launch<SLOTS, 32, 64>(NJ_ARGS);
+#undef NJ_ARGS
+}
+
+// One nn-descent round, as specified above nn_descent_join_kernel, written to
+// G_out / Gd_out (other waves read G while a node's row is written, so the
+// outputs may not share memory with any input). stats, when given, receives
+// the rows of X keyed per node.
+void nn_descent_join(torch::Tensor X, torch::Tensor G, torch::Tensor Gd, torch::Tensor join,
+                     torch::Tensor rev, torch::Tensor G_out, torch::Tensor Gd_out,
+                     c10::optional<torch::Tensor> stats) {
+  for (const torch::Tensor* t : {&X, &Gd, &Gd_out})
+    TORCH_CHECK(t->is_cuda() && t->dtype() == torch::kFloat32 && t->is_contiguous() &&
+                    t->dim() == 2,
+                "nn_descent_join: X, Gd and Gd_out must be contiguous 2-d f32 device tensors");
+  for (const torch::Tensor* t : {&G, &join, &rev, &G_out})
+    TORCH_CHECK(t->is_cuda() && t->dtype() == torch::kInt64 && t->is_contiguous() &&
+                    t->dim() == 2,
+                "nn_descent_join: G, join, rev and G_out must be contiguous 2-d i64 device tensors");
+  const int64_t n = X.size(0), d = X.size(1), deg = G.size(1);
+  const int64_t J = join.size(1), R = rev.size(1);
+  TORCH_CHECK(n < (1LL << 31), "nn_descent_join supports n < 2**31");
+  TORCH_CHECK(d >= 1 && d <= GD_DMAX, "nn_descent_join supports 1 <= d <= 2048");
+  TORCH_CHECK(deg >= 1 && deg <= NJ_MAX_DEG, "nn_descent_join supports 1 <= deg <= 256");
+  TORCH_CHECK(J <= NJ_MAX_JOIN, "nn_descent_join supports at most 64 joined lists per node");
+  TORCH_CHECK(J * deg + R < (1LL << 30), "nn_descent_join: too many candidates per node");
+  for (const torch::Tensor* t : {&G, &Gd, &G_out, &Gd_out})
+    TORCH_CHECK(t->size(0) == n && t->size(1) == deg,
+                "nn_descent_join: G, Gd, G_out and Gd_out must be [n, deg]");
+  TORCH_CHECK(join.size(0) == n && rev.size(0) == n,
+              "nn_descent_join: join and rev need one row per node");
+  for (const torch::Tensor* o : {&G_out, &Gd_out})
+    for (const torch::Tensor* t : {&X, &G, &Gd, &join, &rev})
+      TORCH_CHECK(!nj_overlap(*o, *t), "nn_descent_join: an output buffer aliases an input");
+  TORCH_CHECK(!nj_overlap(G_out, Gd_out), "nn_descent_join: the output buffers alias");
+  int* st = nullptr;
+  if (stats.has_value()) {
+    TORCH_CHECK(stats->is_cuda() && stats->dtype() == torch::kInt32 && stats->is_contiguous() &&
+                    stats->dim() == 1 && stats->size(0) == n,
+                "nn_descent_join: stats must be a contiguous [n] i32 device tensor");
+    st = stats->data_ptr<int32_t>();
+  }
+  if (n == 0) return;
+  const unsigned grid = (unsigned)((n + 3) / 4);
+#define NJ_CALL(S)                                                                        \
+  nn_descent_join_slots<S>(grid, X.data_ptr<float>(), G.data_ptr<int64_t>(),              \
+                           Gd.data_ptr<float>(), join.data_ptr<int64_t>(),                \
+                           rev.data_ptr<int64_t>(), n, (int)d, (int)deg, (int)J, (int)R,  \
+                           G_out.data_ptr<int64_t>(), Gd_out.data_ptr<float>(), st)
+  if (deg <= 64) NJ_CALL(1);
+  else if (deg <= 128) NJ_CALL(2);
+  else NJ_CALL(4);
+#undef NJ_CALL
+}
+
 torch::Tensor fil_predict(torch::Tensor X, torch::Tensor feat, torch::Tensor thr,
                           torch::Tensor left, torch::Tensor right, torch::Tensor value,
                           torch::Tensor roots, bool classif) {
@@ -5042,5 +5408,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("cagra_prune", &cagra_prune,
         "rank-based detour counts of a kNN graph and its rows reordered by them",
         py::arg("G"), py::arg("D_out"));
+  m.def("nn_descent_join", &nn_descent_join,
+        "one nn-descent round: per-node dedup, distances and top-deg selection in one launch",
+        py::arg("X"), py::arg("G"), py::arg("Gd"), py::arg("join"), py::arg("rev"),
+        py::arg("G_out"), py::arg("Gd_out"), py::arg("stats") = py::none());
   m.attr("_is_hip") = true;
 }

@@ -829,6 +829,68 @@ def _reverse_edges(G: torch.Tensor, cap: int) -> torch.Tensor:
     return rev
 
 
+_NND_MAX_DEGREE = 256  # nn_descent_join: widest list the kernel keeps
+# The measured default (RESULTS.md, "nn-descent: fused local join").
+_NND_KERNEL_DEFAULT = True
+
+
+def _nnd_kernel_wanted(X: torch.Tensor, degree: int) -> bool:
+    """Route the nn-descent round through the `nn_descent_join` kernel? On the
+    GPU, for f32 items with d <= 2048, degree <= 256 and n < 2**31.
+    SRML_NND_KERNEL=0 forces the torch round; =1 asks for the kernel, which it
+    gets wherever it is legal; unset takes the measured default. On a GPU
+    without the built extension the kernel path raises, as every HIP path."""
+    from ..ops.dispatch import use_hip
+
+    env = os.environ.get("SRML_NND_KERNEL")
+    if env == "0" or not (X.is_cuda and use_hip(X)):
+        return False
+    if X.dtype != torch.float32 or X.shape[1] > 2048:
+        return False
+    if degree > _NND_MAX_DEGREE or X.shape[0] >= 2**31:
+        return False
+    return env == "1" or _NND_KERNEL_DEFAULT
+
+
+def _nnd_step_torch(
+    X: torch.Tensor, G: torch.Tensor, Gd: torch.Tensor, join: torch.Tensor, rev: torch.Tensor
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One nn-descent round in torch: the lists of the joined nodes and the
+    reverse edges are gathered as one candidate block, keyed by `gather_dists`
+    and merged into (G, Gd) by a row sort and top-k."""
+    n, degree = G.shape
+    rows = torch.arange(n, device=X.device)
+    cand = torch.cat([G[join].reshape(n, -1), rev], dim=1)
+    cd = _batched_dists(X, rows, cand)
+    cat_i = torch.cat([G, cand], dim=1)
+    cat_d = torch.cat([Gd, cd], dim=1)
+    cat_d = torch.where(cat_i == rows[:, None], torch.full_like(cat_d, 3.4e38), cat_d)
+    return _dedup_topk(cat_i, cat_d, degree)
+
+
+def _nnd_step_kernel(
+    X: torch.Tensor,
+    G: torch.Tensor,
+    Gd: torch.Tensor,
+    join: torch.Tensor,
+    rev: torch.Tensor,
+    stats: Optional[torch.Tensor] = None,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The same round in one `nn_descent_join` launch: no candidate block, and
+    a row of X is read only for an id that is new to the node. `stats` ([n]
+    int32), when given, receives the rows keyed per node. A row with fewer
+    distinct candidates than its width ends in (own id, 3.4e38) fillers."""
+    from ..ops.dispatch import hip_ops
+
+    G_out = torch.empty_like(G, memory_format=torch.contiguous_format)
+    Gd_out = torch.empty_like(Gd, memory_format=torch.contiguous_format)
+    hip_ops().nn_descent_join(
+        X.contiguous(), G.contiguous(), Gd.contiguous(), join.contiguous(),
+        rev.contiguous(), G_out, Gd_out, stats,
+    )
+    return G_out, Gd_out
+
+
 def _nn_descent(X: torch.Tensor, degree: int, n_iter: int) -> torch.Tensor:
     """Approximate kNN graph by nn-descent (reference cagra's graph build):
     start from random neighbors, iteratively propose neighbors-of-neighbors
@@ -841,16 +903,12 @@ def _nn_descent(X: torch.Tensor, degree: int, n_iter: int) -> torch.Tensor:
     G = torch.randint(0, n, (n, degree), generator=g).to(device)
     rows = torch.arange(n, device=device)
     Gd = _batched_dists(X, rows, G)
+    step = _nnd_step_kernel if _nnd_kernel_wanted(X, degree) else _nnd_step_torch
     for _ in range(max(1, n_iter)):
         sub_f = G[:, : min(degree, 8)]
         rev = _reverse_edges(G, min(degree, 8))
         join = torch.cat([sub_f, rev], dim=1)  # [n, <=16]
-        cand = torch.cat([G[join].reshape(n, -1), rev], dim=1)
-        cd = _batched_dists(X, rows, cand)
-        cat_i = torch.cat([G, cand], dim=1)
-        cat_d = torch.cat([Gd, cd], dim=1)
-        cat_d = torch.where(cat_i == rows[:, None], torch.full_like(cat_d, 3.4e38), cat_d)
-        G, Gd = _dedup_topk(cat_i, cat_d, degree)
+        G, Gd = step(X, G, Gd, join, rev)
     return G
 
 
