@@ -200,6 +200,234 @@ __global__ __launch_bounds__(256) void kmeans_assign_kernel(
   }
 }
 
+// ---------------------------------------------------------------------------
+// kmeans_assign_f64: the same fused X·C^T + running argmin in f64, for
+// float32_inputs=False. v_mfma_f64_16x16x4_f64: lane l supplies
+// A[i=l&15][k=l>>4] and B[k=l>>4][j=l&15]; C/D element (reg, lane) ->
+// row=4*reg+(lane>>4), col=lane&15 (4 doubles per lane; the exact-integer tests
+// in tests/test_kmeans_f64.py pin this down).
+//
+// Grid: one block per 128-row slice of X, looping over all centre tiles
+// (BN=128) and, per tile, over d in BK=16 steps. 4 waves in a 2x2 grid, each
+// owning 64x64 as 4x4 MFMA tiles (64 accumulator doubles per lane); per
+// 4-wide k step a wave reads 4 + 4 operand doubles from LDS for 16 MFMAs of 16
+// passes each, so the LDS reads hide under the matrix pipe. Tiles are staged
+// k-major with a 132-double row stride: the transposing staging writes of a
+// wave (16 k x 4 rows) then fall 2-way on the banks, which a 64-lane b64
+// write pays anyway, and rows stay 16-byte aligned. Single LDS buffer with the
+// write-after-barrier register pipeline of kmeans_assign_kernel: the next
+// tile's global loads are in flight during the MFMA phase.
+//
+// An f64 score and an index do not pack into a 64-bit atomicMin word, so each
+// lane keeps the running best (score = |c|^2 - 2x·c, index) of its 16 rows in
+// registers over all centre tiles, compared lexicographically (lower index
+// wins an exact tie). One reduction at the end: xor-shuffles over the 16
+// lanes that share a row, then the two waves that share rows meet in LDS.
+// Edge tiles are zero-filled and pad centres are skipped by index, so no
+// shape is illegal. The inertia leaves as one partial per block, summed by
+// the wrapper: no floating atomics, identical bits from run to run.
+//
+// As compiled (ROCm 7.2 clang, -O3): 256 VGPR + 242 AGPR, no scratch, 36,880
+// bytes of LDS -> 1 wave/SIMD. The accumulators live in a[0:127] and the MFMA
+// loop moves nothing between the register files; the AGPRs beyond them hold
+// the running best and the staged tile outside that loop.
+// ---------------------------------------------------------------------------
+
+using f64x4 = __attribute__((ext_vector_type(4))) double;
+
+constexpr int K64_BM = 128;
+constexpr int K64_BN = 128;
+constexpr int K64_BK = 16;
+constexpr int K64_LD = K64_BM + 4;                // LDS row stride in doubles
+constexpr int K64_ST = K64_BK * K64_BM / 256;     // staging elems per thread (8)
+
+__device__ __forceinline__ bool k64_better(double s, int j, double bs, int bj) {
+  return s < bs || (s == bs && j < bj);
+}
+
+__global__ __launch_bounds__(256) void kmeans_assign_f64_kernel(
+    const double* __restrict__ X,     // [n,d] row-major
+    const double* __restrict__ C,     // [k,d] row-major
+    const double* __restrict__ x_sq,  // [n]
+    const double* __restrict__ c_sq,  // [k]
+    int n, int d, int k,
+    int32_t* __restrict__ labels,     // [n]
+    double* __restrict__ min_dists,   // [n] squared distance to the winner
+    double* __restrict__ partials) {  // [grid] inertia of this block's rows
+  __shared__ double lds_x[K64_BK][K64_LD];
+  __shared__ double lds_c[K64_BK][K64_LD];
+  __shared__ double red_s[2][K64_BM];
+  __shared__ int red_j[2][K64_BM];
+  __shared__ double block_inertia[2];
+
+  const int64_t i0 = (int64_t)blockIdx.x * K64_BM;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const int wr = wave >> 1;  // wave row (0..1) -> 64 rows
+  const int wc = wave & 1;   // wave col (0..1) -> 64 cols
+  const int l16 = lane & 15;
+  const int lk = lane >> 4;
+
+  const bool full_rows = (i0 + K64_BM <= n);
+  const int nsteps = (d + K64_BK - 1) / K64_BK;
+  double rx[K64_ST], rc[K64_ST];
+
+  // running best of rows wr*64 + m*16 + 4*r + lk over this lane's columns
+  double bs[4][4];
+  int bj[4][4];
+#pragma unroll
+  for (int m = 0; m < 4; ++m)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      bs[m][r] = INFINITY;
+      bj[m][r] = 0;
+    }
+
+  // loads: K64_ST=8 elems/thread; e = q*256+tid over 2048 = 128 rows x 16 kd
+#define K64_LOAD_T(dst, SRC, base_row, lim, full, d0)                          \
+  do {                                                                         \
+    if ((full) && (d0) + K64_BK <= d) {                                        \
+      _Pragma("unroll") for (int q = 0; q < K64_ST; ++q) {                     \
+        int e = q * 256 + tid;                                                 \
+        dst[q] = SRC[((base_row) + (e >> 4)) * (int64_t)d + (d0) + (e & 15)];  \
+      }                                                                        \
+    } else {                                                                   \
+      _Pragma("unroll") for (int q = 0; q < K64_ST; ++q) {                     \
+        int e = q * 256 + tid;                                                 \
+        int64_t gr = (base_row) + (e >> 4);                                    \
+        int gd = (d0) + (e & 15);                                              \
+        dst[q] = (gr < (lim) && gd < d) ? SRC[gr * (int64_t)d + gd] : 0.0;     \
+      }                                                                        \
+    }                                                                          \
+  } while (0)
+
+#define K64_WRITE()                                                            \
+  do {                                                                         \
+    _Pragma("unroll") for (int q = 0; q < K64_ST; ++q) {                       \
+      int e = q * 256 + tid;                                                   \
+      lds_x[e & 15][e >> 4] = rx[q];                                           \
+      lds_c[e & 15][e >> 4] = rc[q];                                           \
+    }                                                                          \
+  } while (0)
+
+  for (int64_t j0 = 0; j0 < k; j0 += K64_BN) {
+    const bool full_cols = (j0 + K64_BN <= k);
+    f64x4 acc[4][4];
+#pragma unroll
+    for (int m = 0; m < 4; ++m)
+#pragma unroll
+      for (int nn = 0; nn < 4; ++nn)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[m][nn][r] = 0.0;
+
+    // prologue: tile 0 into LDS, tile 1 into regs
+    K64_LOAD_T(rx, X, i0, n, full_rows, 0);
+    K64_LOAD_T(rc, C, j0, k, full_cols, 0);
+    K64_WRITE();  // the previous centre tile ended behind a barrier
+    if (nsteps > 1) {
+      K64_LOAD_T(rx, X, i0, n, full_rows, K64_BK);
+      K64_LOAD_T(rc, C, j0, k, full_cols, K64_BK);
+    }
+    __syncthreads();
+
+    for (int step = 0; step < nsteps; ++step) {
+#pragma unroll
+      for (int kk = 0; kk < K64_BK / 4; ++kk) {
+        const int kd = 4 * kk + lk;
+        double a[4], b[4];
+#pragma unroll
+        for (int m = 0; m < 4; ++m) a[m] = lds_x[kd][wr * 64 + m * 16 + l16];
+#pragma unroll
+        for (int nn = 0; nn < 4; ++nn) b[nn] = lds_c[kd][wc * 64 + nn * 16 + l16];
+#pragma unroll
+        for (int m = 0; m < 4; ++m)
+#pragma unroll
+          for (int nn = 0; nn < 4; ++nn)
+            acc[m][nn] =
+                __builtin_amdgcn_mfma_f64_16x16x4f64(a[m], b[nn], acc[m][nn], 0, 0, 0);
+      }
+      __syncthreads();  // all waves done reading this tile
+      if (step + 1 < nsteps) {
+        K64_WRITE();  // vmcnt-waits for loads issued a full MFMA phase ago
+        if (step + 2 < nsteps) {
+          K64_LOAD_T(rx, X, i0, n, full_rows, (step + 2) * K64_BK);
+          K64_LOAD_T(rc, C, j0, k, full_cols, (step + 2) * K64_BK);
+        }
+        __syncthreads();
+      }
+    }
+
+    // epilogue: scores into the running best; a pad centre never enters
+#pragma unroll
+    for (int nn = 0; nn < 4; ++nn) {
+      const int64_t gj64 = j0 + wc * 64 + nn * 16 + l16;
+      if (gj64 < k) {
+        const int gj = (int)gj64;
+        const double cs = c_sq[gj];
+#pragma unroll
+        for (int m = 0; m < 4; ++m)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const double s = cs - 2.0 * acc[m][nn][r];
+            if (k64_better(s, gj, bs[m][r], bj[m][r])) {
+              bs[m][r] = s;
+              bj[m][r] = gj;
+            }
+          }
+      }
+    }
+  }
+#undef K64_LOAD_T
+#undef K64_WRITE
+
+  // the 16 lanes that share a row, then the two waves that share it
+#pragma unroll
+  for (int m = 0; m < 4; ++m)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      double s = bs[m][r];
+      int j = bj[m][r];
+#pragma unroll
+      for (int off = 1; off < 16; off <<= 1) {
+        const double so = __shfl_xor(s, off, 64);
+        const int jo = __shfl_xor(j, off, 64);
+        if (k64_better(so, jo, s, j)) {
+          s = so;
+          j = jo;
+        }
+      }
+      if (l16 == 0) {
+        const int row = wr * 64 + m * 16 + 4 * r + lk;
+        red_s[wc][row] = s;
+        red_j[wc][row] = j;
+      }
+    }
+  __syncthreads();
+
+  double dist = 0.0;
+  if (tid < K64_BM) {
+    double s = red_s[0][tid];
+    int j = red_j[0][tid];
+    if (k64_better(red_s[1][tid], red_j[1][tid], s, j)) {
+      s = red_s[1][tid];
+      j = red_j[1][tid];
+    }
+    const int64_t gi = i0 + tid;
+    if (gi < n) {
+      dist = fmax(0.0, x_sq[gi] + s);
+      labels[gi] = j;
+      min_dists[gi] = dist;
+    }
+  }
+  // fixed-order block sum: shuffle tree per wave, then wave 0 + wave 1
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) dist += __shfl_down(dist, off, 64);
+  if (lane == 0 && wave < 2) block_inertia[wave] = dist;
+  __syncthreads();
+  if (tid == 0) partials[blockIdx.x] = block_inertia[0] + block_inertia[1];
+}
+
 
 
 
@@ -543,6 +771,128 @@ __global__ __launch_bounds__(256) void segment_sum_kernel(
       }
     }
   }
+}
+
+// ---------------------------------------------------------------------------
+// segment_sum_f64: segment_sum for f64 rows, bitwise repeatable. Same sorted
+// segments and (label, split) blocks, double accumulators, but each block
+// writes its stripe of an [LA_SPLIT, k, d] partial buffer (zeros for an empty
+// sub-segment, so the buffer needs no clearing) and segment_reduce_f64 adds
+// the LA_SPLIT partials in split order: no atomics. Counts come from the
+// segment offsets in the wrapper.
+//
+// Work split: `tpr` threads (a power of two, chosen by the wrapper) cover one
+// row, W columns per load (VEC: double2, d even and a 16-byte aligned base),
+// up to LA64_COLS loads per thread and row, 4 rows in flight. Where a row
+// needs fewer than 256 threads the block's 256 / tpr thread groups take rows
+// g, g + G, ... of the sub-segment and meet in LDS in group order, so narrow
+// rows still fill the block's loads.
+// ---------------------------------------------------------------------------
+
+constexpr int LA64_COLS = 8;  // loads per thread and row (256*8*2 = 4096 columns a pass)
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void segment_sum_f64_kernel(
+    const double* __restrict__ X, const int64_t* __restrict__ perm,
+    const int64_t* __restrict__ seg_off, int d, int tpr,
+    double* __restrict__ part) {  // [LA_SPLIT, k, d]
+  constexpr int W = VEC ? 2 : 1;
+  __shared__ double red[256 * W];
+  const int k = gridDim.x / LA_SPLIT;
+  const int lab = blockIdx.x / LA_SPLIT;
+  const int split = blockIdx.x % LA_SPLIT;
+  const int64_t s0 = seg_off[lab], e0 = seg_off[lab + 1];
+  const int64_t chunk = (e0 - s0 + LA_SPLIT - 1) / LA_SPLIT;
+  const int64_t rs = min(e0, s0 + split * chunk);
+  const int64_t re = min(e0, rs + chunk);
+  const int G = 256 / tpr;            // row groups in the block
+  const int g = threadIdx.x / tpr;    // this thread's group
+  const int t = threadIdx.x % tpr;    // and its place along the row
+  double* __restrict__ out = part + ((int64_t)split * k + lab) * d;
+
+  auto load = [&](const double* row, int c, double* v) {
+    if constexpr (VEC) {
+      const double2 p = *reinterpret_cast<const double2*>(row + c);
+      v[0] = p.x;
+      v[1] = p.y;
+    } else {
+      v[0] = row[c];
+    }
+  };
+
+  for (int cb = 0; cb < d; cb += tpr * W * LA64_COLS) {
+    double acc[LA64_COLS][W];
+#pragma unroll
+    for (int q = 0; q < LA64_COLS; ++q)
+#pragma unroll
+      for (int w = 0; w < W; ++w) acc[q][w] = 0.0;
+    int64_t r = rs + g;
+    for (; r + 3 * (int64_t)G < re; r += 4 * G) {  // 4 rows in flight
+      const double* row0 = X + perm[r] * (int64_t)d;
+      const double* row1 = X + perm[r + G] * (int64_t)d;
+      const double* row2 = X + perm[r + 2 * G] * (int64_t)d;
+      const double* row3 = X + perm[r + 3 * G] * (int64_t)d;
+#pragma unroll
+      for (int q = 0; q < LA64_COLS; ++q) {
+        const int c = cb + (q * tpr + t) * W;
+        if (c < d) {
+          double v0[W], v1[W], v2[W], v3[W];
+          load(row0, c, v0);
+          load(row1, c, v1);
+          load(row2, c, v2);
+          load(row3, c, v3);
+#pragma unroll
+          for (int w = 0; w < W; ++w) acc[q][w] += (v0[w] + v1[w]) + (v2[w] + v3[w]);
+        }
+      }
+    }
+    for (; r < re; r += G) {
+      const double* row = X + perm[r] * (int64_t)d;
+#pragma unroll
+      for (int q = 0; q < LA64_COLS; ++q) {
+        const int c = cb + (q * tpr + t) * W;
+        if (c < d) {
+          double v[W];
+          load(row, c, v);
+#pragma unroll
+          for (int w = 0; w < W; ++w) acc[q][w] += v[w];
+        }
+      }
+    }
+    if (G > 1) {  // tpr * W >= d: one pass, and only q = 0 holds columns
+#pragma unroll
+      for (int w = 0; w < W; ++w) red[threadIdx.x * W + w] = acc[0][w];
+      __syncthreads();
+      const int c = t * W;
+      if (g == 0 && c < d) {
+#pragma unroll
+        for (int w = 0; w < W; ++w) {
+          double s = 0.0;
+          for (int gg = 0; gg < G; ++gg) s += red[(gg * tpr + t) * W + w];
+          out[c + w] = s;
+        }
+      }
+    } else {
+#pragma unroll
+      for (int q = 0; q < LA64_COLS; ++q) {
+        const int c = cb + (q * tpr + t) * W;
+        if (c < d) {
+#pragma unroll
+          for (int w = 0; w < W; ++w) out[c + w] = acc[q][w];
+        }
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void segment_reduce_f64_kernel(
+    const double* __restrict__ part, int64_t kd, double* __restrict__ sums) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= kd) return;
+  double s = part[i];
+#pragma unroll
+  for (int sp = 1; sp < LA_SPLIT; ++sp) s += part[sp * kd + i];
+  sums[i] = s;
 }
 
 // ---------------------------------------------------------------------------
@@ -4288,6 +4638,87 @@ std::vector<torch::Tensor> label_accumulate_inertia(torch::Tensor X, torch::Tens
   return {sums, counts, inertia};
 }
 
+// (labels i32 [n], min_dists f64 [n], inertia f64 [1]) for f64 X, C and |x|^2.
+// Any n < 2^31, k >= 1, d >= 1: the kernel zero-fills its edge tiles. The
+// inertia is the fixed-order sum of the per-block partials.
+std::vector<torch::Tensor> kmeans_assign_f64(torch::Tensor X, torch::Tensor C,
+                                             torch::Tensor x_sq) {
+  TORCH_CHECK(X.is_cuda() && C.is_cuda() && x_sq.is_cuda(), "device tensors required");
+  TORCH_CHECK(X.dtype() == torch::kFloat64 && C.dtype() == torch::kFloat64 &&
+                  x_sq.dtype() == torch::kFloat64,
+              "kmeans_assign_f64 takes f64 X, C and x_sq");
+  TORCH_CHECK(X.dim() == 2 && C.dim() == 2 && x_sq.dim() == 1);
+  TORCH_CHECK(X.is_contiguous() && C.is_contiguous() && x_sq.is_contiguous());
+  TORCH_CHECK(C.size(1) == X.size(1), "X and C column counts disagree");
+  TORCH_CHECK(x_sq.numel() == X.size(0), "one |x|^2 per row");
+  const int64_t n = X.size(0);
+  TORCH_CHECK(n < (int64_t(1) << 31) && C.size(0) < (int64_t(1) << 31) &&
+                  X.size(1) < (int64_t(1) << 31),
+              "n, k and d must be below 2^31");
+  auto labels = torch::empty({n}, X.options().dtype(torch::kInt32));
+  auto min_dists = torch::empty({n}, X.options());
+  if (n == 0) return {labels, min_dists, torch::zeros({1}, X.options())};
+  TORCH_CHECK(C.size(0) >= 1 && X.size(1) >= 1, "needs k >= 1 and d >= 1");
+  auto c_sq = (C * C).sum(1).contiguous();
+  const int64_t grid = (n + K64_BM - 1) / K64_BM;
+  auto partials = torch::empty({grid}, X.options());
+  hipLaunchKernelGGL(kmeans_assign_f64_kernel, dim3((unsigned)grid), dim3(256), 0,
+                     cur_stream(), X.data_ptr<double>(), C.data_ptr<double>(),
+                     x_sq.data_ptr<double>(), c_sq.data_ptr<double>(), (int)n,
+                     (int)X.size(1), (int)C.size(0), labels.data_ptr<int32_t>(),
+                     min_dists.data_ptr<double>(), partials.data_ptr<double>());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return {labels, min_dists, partials.sum().reshape({1})};
+}
+
+// (sums f64 [k,d], counts f64 [k]) from f64 rows on the sorted segment path.
+// The sort is stable, so each segment keeps row order and the sums are the
+// same bits on every run.
+std::vector<torch::Tensor> label_accumulate_f64(torch::Tensor X, torch::Tensor labels,
+                                                int64_t k) {
+  TORCH_CHECK(X.is_cuda() && labels.is_cuda(), "device tensors required");
+  TORCH_CHECK(X.dtype() == torch::kFloat64 && X.is_contiguous() && X.dim() == 2,
+              "label_accumulate_f64 takes a contiguous f64 [n, d] X");
+  TORCH_CHECK(labels.dtype() == torch::kInt32 || labels.dtype() == torch::kInt64,
+              "labels must be i32 or i64");
+  TORCH_CHECK(labels.dim() == 1 && labels.numel() == X.size(0), "one label per row");
+  TORCH_CHECK(k >= 0 && k * LA_SPLIT < (int64_t(1) << 31) && X.size(1) < (int64_t(1) << 31),
+              "k or d out of range");
+  const int64_t n = X.size(0);
+  const int d = (int)X.size(1);
+  auto sums = torch::zeros({k, d}, X.options());
+  auto counts = torch::zeros({k}, X.options());
+  if (n == 0 || k == 0 || d == 0) return {sums, counts};
+  auto sorted = labels.to(torch::kInt64).sort(/*stable=*/true, 0, false);
+  auto perm = std::get<1>(sorted).contiguous();
+  auto sl = std::get<0>(sorted).contiguous();
+  auto bounds = torch::arange(k + 1, labels.options().dtype(torch::kInt64));
+  auto seg_off = torch::searchsorted(sl, bounds).contiguous();
+  counts = seg_off.diff().to(torch::kFloat64);
+  auto part = torch::empty({(int64_t)LA_SPLIT, k, (int64_t)d}, X.options());
+  const bool vec = d % 2 == 0 && (uintptr_t)X.data_ptr() % 16 == 0;
+  const int per_row = vec ? d / 2 : d;  // threads one row can use
+  int tpr = 1;
+  while (tpr < 256 && tpr < per_row) tpr *= 2;
+  if (vec)
+    hipLaunchKernelGGL(segment_sum_f64_kernel<true>, dim3((unsigned)(k * LA_SPLIT)),
+                       dim3(256), 0, cur_stream(), X.data_ptr<double>(),
+                       perm.data_ptr<int64_t>(), seg_off.data_ptr<int64_t>(), d, tpr,
+                       part.data_ptr<double>());
+  else
+    hipLaunchKernelGGL(segment_sum_f64_kernel<false>, dim3((unsigned)(k * LA_SPLIT)),
+                       dim3(256), 0, cur_stream(), X.data_ptr<double>(),
+                       perm.data_ptr<int64_t>(), seg_off.data_ptr<int64_t>(), d, tpr,
+                       part.data_ptr<double>());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  const int64_t kd = k * (int64_t)d;
+  hipLaunchKernelGGL(segment_reduce_f64_kernel, dim3((unsigned)((kd + 255) / 256)),
+                     dim3(256), 0, cur_stream(), part.data_ptr<double>(), kd,
+                     sums.data_ptr<double>());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return {sums, counts};
+}
+
 torch::Tensor gram_f32(torch::Tensor A) {
   TORCH_CHECK(A.is_cuda() && A.dtype() == torch::kFloat32 && A.is_contiguous());
   const int64_t n = A.size(0);
@@ -5362,6 +5793,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("csr_grad", &csr_grad, "CSR grad = (A^T R)^T by column scatter");
   m.def("csr_col_moments", &csr_col_moments, "per-column sum/sumsq of CSR values");
   m.def("kmeans_assign", &kmeans_assign, "fused MFMA distance + argmin");
+  m.def("kmeans_assign_f64", &kmeans_assign_f64,
+        "fused f64 MFMA distance + register-resident argmin; per-block inertia partials");
+  m.def("label_accumulate_f64", &label_accumulate_f64,
+        "sorted per-center sum/count from f64 rows, partials reduced in a fixed order");
   m.def("kmeans_argmin_kn", &kmeans_argmin_kn, "argmin epilogue over a [k,n] GEMM dot block");
   m.def("kmeans_argmin_nk", &kmeans_argmin_nk, "argmin epilogue over a row-major [m,k] GEMM dot block");
   m.def("kmeans_split_bf16", &kmeans_split_bf16, "centre + split f32 rows into bf16 hi|lo halves, with |x'|^2");

@@ -28,6 +28,15 @@ over X. A chunk with too many near-ties adds the other two terms onto the
 same dot block. That path reports the inertia `label_accumulate_inertia`
 sums beside the accumulation, as (x − c)² directly.
 
+f64 rows (float32_inputs=False) have a path of their own, `_step_f64`:
+`kmeans_assign_f64` forms c² − 2x·c on mfma_f64_16x16x4f64 with the running
+(score, index) argmin in registers (lower index on an exact tie) and per-block
+inertia partials, and `label_accumulate_f64` sums the sorted segments in
+doubles into per-split partials reduced in a fixed order. Neither uses a
+floating atomic, so a step is bitwise repeatable; any n, k, d is legal.
+SRML_KMEANS_VARIANT, the prepared-X cache and the resident kernel are f32-only
+and are not consulted. `kmeans_predict` takes the same assign kernel.
+
 Together these are the KMeansMG Lloyd-step kernel family of the reference
 (clustering.py:381-415).
 """
@@ -67,7 +76,12 @@ def kmeans_assign_reduce(
     SRML_KMEANS_CACHE=0 turns the cache off.
 
     At k < 384 a contiguous f32 device X whose centres fit in LDS takes the
-    one-pass `kmeans_step_resident` kernel (`_resident_wanted`)."""
+    one-pass `kmeans_step_resident` kernel (`_resident_wanted`).
+
+    An f64 device X (float32_inputs=False) takes `_step_f64`: everything
+    above is f32-only and is not consulted for it."""
+    if use_hip(X) and X.dtype == torch.float64:
+        return _step_f64(hip_ops(), X, C, x_sq)
     if use_hip(X) and X.dtype == torch.float32:
         ext = hip_ops()
         if x_sq is None:
@@ -149,7 +163,27 @@ def _step_resident(
     return labels, sums, counts, float(inertia.item())
 
 
+def _step_f64(
+    ext, X: torch.Tensor, C: torch.Tensor, x_sq: Optional[torch.Tensor]
+) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, float]:
+    """One Lloyd step on f64 rows: `kmeans_assign_f64` (f64 MFMA, argmin kept
+    in registers) + `label_accumulate_f64`. No floating atomics in either, so
+    a repeated call returns the same bits."""
+    X = X.contiguous()
+    x_sq = _xsq(X) if x_sq is None else x_sq.to(torch.float64).contiguous()
+    labels, _min_d, inertia = ext.kmeans_assign_f64(
+        X, C.to(torch.float64).contiguous(), x_sq
+    )
+    sums, counts = ext.label_accumulate_f64(X, labels, C.shape[0])
+    return labels, sums, counts, float(inertia.item())
+
+
 def kmeans_predict(X: torch.Tensor, C: torch.Tensor) -> torch.Tensor:
+    if use_hip(X) and X.dtype == torch.float64:
+        X = X.contiguous()
+        return hip_ops().kmeans_assign_f64(
+            X, C.to(torch.float64).contiguous(), _xsq(X)
+        )[0]
     if use_hip(X) and X.dtype == torch.float32:
         X = X.contiguous()
         return _assign(hip_ops(), X, C, _xsq(X))[0]

@@ -33,9 +33,10 @@ def kmeans_assign_reduce(
     inertia = torch.zeros((), dtype=torch.float64, device=dev)
     if n == 0:
         return labels, sums, counts, 0.0
-    c_sq = (C.to(torch.float32) ** 2).sum(dim=1)
+    # in X's dtype: f64 rows get an f64 expansion, f32 rows the one they had
+    c_sq = (C.to(X.dtype) ** 2).sum(dim=1)
     if x_sq is None:
-        x_sq = (X.to(torch.float32) ** 2).sum(dim=1)
+        x_sq = (X**2).sum(dim=1)
     for s in range(0, n, chunk):
         e = min(n, s + chunk)
         xb = X[s:e]
