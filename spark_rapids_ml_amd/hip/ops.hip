@@ -1273,6 +1273,295 @@ __global__ void gram_mirror_kernel(float* __restrict__ out, int d) {
 }
 
 // ---------------------------------------------------------------------------
+// moments_f64: M = Z^T Z in f64 for Z = [X | 1 | y] ([n, da], da = d + 1 or
+// d + 2), the whole moment set of PCA and linear regression in one pass over
+// X: M[:d,:d] = X^T X, M[:d,d] = column sums, M[d,d] = n, M[:d,d+1] = X^T y,
+// M[d,d+1] = sum y, M[d+1,d+1] = sum y^2. The ones column and y are made in
+// the staging loads (column == d gives 1.0, column == d + 1 gives y[row]); no
+// augmented copy of X exists. Rows >= n and columns >= da stage as 0.
+//
+// Work split: blocks cover the upper-triangle 128x128 tiles of M (bi <= bj,
+// gram_kernel's enumeration) times a row split; the tile index runs fastest,
+// so the blocks in flight walk the same rows of X and share its panels in L2.
+// 4 waves in a 2x2 grid, each 64x64 as 4x4 tiles of v_mfma_f64_16x16x4_f64
+// (64 accumulator doubles per lane; lane layout above kmeans_assign_f64_kernel).
+// A wave issues only the MFMAs of its 16-wide sub-tiles that hold a column
+// below da (EDGE phase): the tile that carries just the ones column and y
+// costs 1/4 of a full one, not a full one.
+//
+// Data movement: a TN product reduces over X's row index, so a staged panel
+// [MO_BK rows][128 columns] is already k-major: 64 lanes read one 1 KB row of
+// the panel (double2 each when d is even and X is 16-byte aligned, VEC), write
+// it to LDS contiguously, and nothing is transposed. A diagonal tile stages
+// one panel and uses it for both operands. For an MFMA a lane reads
+// lds[k = lane >> 4][col0 + (lane & 15)]. Banks: a double covers two 4-byte
+// banks, so the 64 banks are 32 double slots and a 64-lane b64 read takes two
+// passes of 32 lanes at best. The row stride is MO_LD = 144 doubles, 144 mod
+// 32 = 16: k-rows 0 and 1 (lanes 0..31) start 16 slots apart and cover all 32
+// slots once, k-rows 2 and 3 (lanes 32..63) likewise, so both passes are
+// conflict-free. (A stride of 128 would put all four k-rows on the same 16
+// slots, 4-way; 132 leaves rows 0 and 1 overlapping in 12 slots.) Rows stay
+// 16-byte aligned for the double2 staging writes.
+//
+// Pipeline: one LDS buffer per operand with the write-after-barrier register
+// pipeline of kmeans_assign_kernel; the loads of panel s + 2 are in flight
+// during the MFMA phase of panel s + 1. MO_BK = 32: 128 MFMAs a phase (about
+// 3.4 us), twice what the BK = 16 phase of kmeans_assign_f64_kernel had to
+// cover its loads with; the staging is 16 doubles per thread and panel and
+// compiles without scratch.
+//
+// No floating atomics: every (slice, tile) block writes its 128x128 tile to a
+// workspace [split][tiles][128*128]; moments_reduce_f64_kernel adds the slices
+// in slice order, compensated, and writes M[i][j] and M[j][i] (with split 1
+// it only mirrors). The split depends on (n, da) alone, so the bits are the same from
+// run to run and from device to device.
+//
+// As compiled (ROCm 7.2 clang, -O3, -Rpass-analysis=kernel-resource-usage):
+// moments_f64_kernel<true> (double2 loads) 216 VGPR + 128 AGPR, <false> 256
+// VGPR + 194 AGPR; both no scratch, no spills, 73,728 bytes of LDS, 1
+// wave/SIMD. moments_reduce_f64_kernel: 10 VGPR, no LDS, no scratch, 8
+// waves/SIMD.
+// ---------------------------------------------------------------------------
+
+constexpr int MO_BT = 128;                       // output tile edge
+constexpr int MO_BK = 32;                        // rows of X per panel
+constexpr int MO_LD = MO_BT + 16;                // LDS row stride in doubles
+constexpr int MO_ST = MO_BK * MO_BT / 256;       // staged doubles per thread and panel (16)
+constexpr int MO_TILE = MO_BT * MO_BT;
+
+// tile number -> (stripe b, offset o <= b): rows o*128.., columns b*128..
+__device__ __forceinline__ void mo_tile(int tri, int& o, int& b) {
+  b = (int)((sqrtf(8.0f * tri + 1.0f) - 1.0f) * 0.5f);
+  while ((int64_t)(b + 1) * (b + 2) / 2 <= tri) ++b;
+  while ((int64_t)b * (b + 1) / 2 > tri) --b;
+  o = tri - (int)((int64_t)b * (b + 1) / 2);
+}
+
+// rows r0 .. r0 + MO_BK, columns col0 .. col0 + 128 of Z into registers
+template <bool VEC>
+__device__ __forceinline__ void mo_load(const double* __restrict__ X,
+                                        const double* __restrict__ y, int64_t n, int d,
+                                        int64_t r0, int col0, int tid, double (&rg)[MO_ST]) {
+  const bool fast = (col0 + MO_BT <= d) && (r0 + MO_BK <= n);
+  if constexpr (VEC) {
+    if (fast) {
+#pragma unroll
+      for (int q = 0; q < MO_ST / 2; ++q) {
+        const int e = q * 256 + tid;
+        const double2 p = *reinterpret_cast<const double2*>(
+            X + (r0 + (e >> 6)) * (int64_t)d + col0 + 2 * (e & 63));
+        rg[2 * q] = p.x;
+        rg[2 * q + 1] = p.y;
+      }
+    } else {
+#pragma unroll
+      for (int q = 0; q < MO_ST / 2; ++q) {
+        const int e = q * 256 + tid;
+        const int64_t gr = r0 + (e >> 6);
+        const int gc = col0 + 2 * (e & 63);  // even, as d is: the pair never straddles d
+        double v0 = 0.0, v1 = 0.0;
+        if (gr < n) {
+          if (gc < d) {
+            const double2 p = *reinterpret_cast<const double2*>(X + gr * (int64_t)d + gc);
+            v0 = p.x;
+            v1 = p.y;
+          } else if (gc == d) {
+            v0 = 1.0;
+            if (y != nullptr) v1 = y[gr];
+          }
+        }
+        rg[2 * q] = v0;
+        rg[2 * q + 1] = v1;
+      }
+    }
+  } else {
+    if (fast) {
+#pragma unroll
+      for (int q = 0; q < MO_ST; ++q) {
+        const int e = q * 256 + tid;
+        rg[q] = X[(r0 + (e >> 7)) * (int64_t)d + col0 + (e & 127)];
+      }
+    } else {
+#pragma unroll
+      for (int q = 0; q < MO_ST; ++q) {
+        const int e = q * 256 + tid;
+        const int64_t gr = r0 + (e >> 7);
+        const int gc = col0 + (e & 127);
+        double v = 0.0;
+        if (gr < n) {
+          if (gc < d) v = X[gr * (int64_t)d + gc];
+          else if (gc == d) v = 1.0;
+          else if (gc == d + 1 && y != nullptr) v = y[gr];
+        }
+        rg[q] = v;
+      }
+    }
+  }
+}
+
+template <bool VEC>
+__device__ __forceinline__ void mo_write(double (*lds)[MO_LD], int tid,
+                                         const double (&rg)[MO_ST]) {
+  if constexpr (VEC) {
+#pragma unroll
+    for (int q = 0; q < MO_ST / 2; ++q) {
+      const int e = q * 256 + tid;
+      *reinterpret_cast<double2*>(&lds[e >> 6][2 * (e & 63)]) =
+          make_double2(rg[2 * q], rg[2 * q + 1]);
+    }
+  } else {
+#pragma unroll
+    for (int q = 0; q < MO_ST; ++q) {
+      const int e = q * 256 + tid;
+      lds[e >> 7][e & 127] = rg[q];
+    }
+  }
+}
+
+// one panel's MFMAs; EDGE issues only sub-tiles (m < mlive, nn < nlive)
+template <bool EDGE>
+__device__ __forceinline__ void mo_mfma_phase(const double (*pi)[MO_LD],
+                                              const double (*pj)[MO_LD], int rowoff,
+                                              int coloff, int lk, int mlive, int nlive,
+                                              f64x4 (&acc)[4][4]) {
+#pragma unroll
+  for (int kk = 0; kk < MO_BK / 4; ++kk) {
+    const int kr = 4 * kk + lk;
+    double a[4], b[4];
+#pragma unroll
+    for (int m = 0; m < 4; ++m) a[m] = pi[kr][rowoff + m * 16];
+#pragma unroll
+    for (int nn = 0; nn < 4; ++nn) b[nn] = pj[kr][coloff + nn * 16];
+#pragma unroll
+    for (int m = 0; m < 4; ++m)
+#pragma unroll
+      for (int nn = 0; nn < 4; ++nn)
+        if (!EDGE || (m < mlive && nn < nlive))
+          acc[m][nn] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[m], b[nn], acc[m][nn], 0, 0, 0);
+  }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void moments_f64_kernel(
+    const double* __restrict__ X,  // [n,d] row-major
+    const double* __restrict__ y,  // [n] or null
+    int64_t n, int d, int da, int ntiles,
+    int64_t per,                   // panels per row slice
+    double* __restrict__ ws) {     // [gridDim.x / ntiles][ntiles][128*128]
+  __shared__ double lds_i[MO_BK][MO_LD];
+  __shared__ double lds_j[MO_BK][MO_LD];
+
+  const int tri = blockIdx.x % ntiles;
+  const int slice = blockIdx.x / ntiles;
+  int o, b;
+  mo_tile(tri, o, b);
+  const int i0 = o * MO_BT;  // rows of M
+  const int j0 = b * MO_BT;  // columns of M, j0 >= i0
+  const bool diag = (o == b);
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const int wr = wave >> 1;
+  const int wc = wave & 1;
+  const int l16 = lane & 15;
+  const int lk = lane >> 4;
+
+  const int64_t nsteps = (n + MO_BK - 1) / MO_BK;
+  const int64_t s_begin = min(nsteps, slice * per);
+  const int64_t s_end = min(nsteps, s_begin + per);
+
+  // 16-wide sub-tiles of this wave with a column below da
+  const int mlive = max(0, min(4, (da - (i0 + wr * 64) + 15) / 16));
+  const int nlive = max(0, min(4, (da - (j0 + wc * 64) + 15) / 16));
+  const bool edge = (mlive < 4) || (nlive < 4);
+
+  f64x4 acc[4][4];
+#pragma unroll
+  for (int m = 0; m < 4; ++m)
+#pragma unroll
+    for (int nn = 0; nn < 4; ++nn)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) acc[m][nn][r] = 0.0;
+
+  double ri[MO_ST], rj[MO_ST];
+  const double (*pj)[MO_LD] = diag ? lds_i : lds_j;
+
+  if (s_begin < s_end) {
+    mo_load<VEC>(X, y, n, d, s_begin * MO_BK, i0, tid, ri);
+    if (!diag) mo_load<VEC>(X, y, n, d, s_begin * MO_BK, j0, tid, rj);
+    mo_write<VEC>(lds_i, tid, ri);
+    if (!diag) mo_write<VEC>(lds_j, tid, rj);
+    if (s_begin + 1 < s_end) {
+      mo_load<VEC>(X, y, n, d, (s_begin + 1) * MO_BK, i0, tid, ri);
+      if (!diag) mo_load<VEC>(X, y, n, d, (s_begin + 1) * MO_BK, j0, tid, rj);
+    }
+    __syncthreads();
+  }
+
+  for (int64_t step = s_begin; step < s_end; ++step) {
+    if (edge)
+      mo_mfma_phase<true>(lds_i, pj, wr * 64 + l16, wc * 64 + l16, lk, mlive, nlive, acc);
+    else
+      mo_mfma_phase<false>(lds_i, pj, wr * 64 + l16, wc * 64 + l16, lk, 4, 4, acc);
+    __syncthreads();  // all waves done reading this panel
+    if (step + 1 < s_end) {
+      mo_write<VEC>(lds_i, tid, ri);  // vmcnt-waits for loads issued a full MFMA phase ago
+      if (!diag) mo_write<VEC>(lds_j, tid, rj);
+      if (step + 2 < s_end) {
+        mo_load<VEC>(X, y, n, d, (step + 2) * MO_BK, i0, tid, ri);
+        if (!diag) mo_load<VEC>(X, y, n, d, (step + 2) * MO_BK, j0, tid, rj);
+      }
+      __syncthreads();
+    }
+  }
+
+  // every live sub-tile, the zeros of an empty slice included: the reduce
+  // kernel reads every slice, and nothing at or beyond column da
+  double* __restrict__ tile = ws + (int64_t)blockIdx.x * MO_TILE;
+#pragma unroll
+  for (int m = 0; m < 4; ++m)
+#pragma unroll
+    for (int nn = 0; nn < 4; ++nn)
+      if (m < mlive && nn < nlive) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = wr * 64 + m * 16 + 4 * r + lk;
+          const int col = wc * 64 + nn * 16 + l16;
+          tile[row * MO_BT + col] = acc[m][nn][r];
+        }
+      }
+}
+
+// M[i][j] = M[j][i] = sum over slices, in slice order, of the workspace tiles,
+// compensated so that the sum of the slices is rounded once. One thread per
+// tile element, 64 blocks per tile.
+__global__ __launch_bounds__(256) void moments_reduce_f64_kernel(
+    const double* __restrict__ ws, int ntiles, int split, int da,
+    double* __restrict__ M) {  // [da, da]
+  const int tri = blockIdx.x >> 6;
+  const int e = ((blockIdx.x & 63) << 8) + threadIdx.x;
+  int o, b;
+  mo_tile(tri, o, b);
+  const int gi = o * MO_BT + (e >> 7);
+  const int gj = b * MO_BT + (e & 127);
+  if (gi >= da || gj >= da || gj < gi) return;
+  const double* p = ws + (int64_t)tri * MO_TILE + e;
+  // compensated (Neumaier): c collects what each s + v rounds away, so up to
+  // 1536 slices cost one rounding, not one each
+  double s = p[0], c = 0.0;
+  for (int sp = 1; sp < split; ++sp) {
+    const double v = p[(int64_t)sp * ntiles * MO_TILE];
+    const double t = s + v;
+    c += (fabs(s) >= fabs(v)) ? (s - t) + v : (v - t) + s;
+    s = t;
+  }
+  s += c;
+  M[(int64_t)gi * da + gj] = s;
+  M[(int64_t)gj * da + gi] = s;
+}
+
+// ---------------------------------------------------------------------------
 // knn_select: fused brute-force k-NN — MFMA distance tiles + in-LDS
 // per-query top-k (reference NearestNeighborsMG's tiled ||x-y||^2 + top-k
 // merge, SURVEY.md §2.3b knn.py:763-774). No [nq, ni] distance matrix is
@@ -4740,6 +5029,70 @@ torch::Tensor gram_f32(torch::Tensor A) {
   return out;
 }
 
+// Row split of moments_f64 for (n, da): about 6 blocks per CU of a 256-CU
+// part over tiles x split, no slice shorter than 2 panels, and no empty slice.
+// Short slices are the accuracy of the sum: a slice is one sequential f64
+// chain, whose rounding error grows with its length (about 0.3 L / sqrt(n)
+// ulps of the result for L rows a slice), while the reduce over the slices
+// is compensated. Where the block budget allows, small problems therefore get
+// 64-row slices; their launches are latency-bound either way.
+// tiles x split <= 1536 bounds the workspace at 192 MiB wherever the split is
+// above 1; with split 1 it is the padded upper triangle of M. A function of
+// the shape alone, so the summation order never depends on the device.
+static inline int64_t moments_f64_split(int64_t n, int64_t da) {
+  const int64_t nb = (da + MO_BT - 1) / MO_BT;
+  const int64_t tiles = nb * (nb + 1) / 2;
+  const int64_t nsteps = (n + MO_BK - 1) / MO_BK;
+  const int64_t want = std::max<int64_t>(1, std::min<int64_t>(1536 / tiles, nsteps / 2));
+  const int64_t per = (nsteps + want - 1) / want;
+  return std::max<int64_t>(1, (nsteps + per - 1) / per);
+}
+
+// M = [X | 1 | y]^T [X | 1 | y], f64 [da, da] with da = d + 1 (+ 1 with y).
+// Any n >= 0 and d >= 1; n == 0 returns zeros without a launch.
+torch::Tensor moments_f64(torch::Tensor X, c10::optional<torch::Tensor> y) {
+  TORCH_CHECK(X.is_cuda() && X.dtype() == torch::kFloat64 && X.dim() == 2 && X.is_contiguous(),
+              "moments_f64 takes a contiguous f64 [n, d] device X");
+  const int64_t n = X.size(0);
+  const int64_t d64 = X.size(1);
+  TORCH_CHECK(d64 >= 1 && d64 < (int64_t(1) << 31) - 256, "d out of range");
+  const double* yp = nullptr;
+  if (y.has_value()) {
+    TORCH_CHECK(y->is_cuda() && y->dtype() == torch::kFloat64 && y->dim() == 1 &&
+                    y->is_contiguous() && y->numel() == n,
+                "y must be a contiguous f64 [n] device tensor");
+    yp = y->data_ptr<double>();
+  }
+  const int d = (int)d64;
+  const int da = d + (y.has_value() ? 2 : 1);
+  if (n == 0) return torch::zeros({da, da}, X.options());
+  const int64_t nb = (da + MO_BT - 1) / MO_BT;
+  const int64_t tiles = nb * (nb + 1) / 2;
+  const int64_t split = moments_f64_split(n, da);
+  const int64_t nsteps = (n + MO_BK - 1) / MO_BK;
+  const int64_t per = (nsteps + split - 1) / split;
+  TORCH_CHECK(tiles * split < (int64_t(1) << 31) && tiles * 64 < (int64_t(1) << 31),
+              "too many tiles");
+  auto ws = torch::empty({split * tiles, (int64_t)MO_TILE}, X.options());
+  auto M = torch::empty({da, da}, X.options());
+  const bool vec = d % 2 == 0 && (uintptr_t)X.data_ptr() % 16 == 0;
+  const dim3 grid((unsigned)(tiles * split));
+  if (vec)
+    hipLaunchKernelGGL(moments_f64_kernel<true>, grid, dim3(256), 0, cur_stream(),
+                       X.data_ptr<double>(), yp, n, d, da, (int)tiles, per,
+                       ws.data_ptr<double>());
+  else
+    hipLaunchKernelGGL(moments_f64_kernel<false>, grid, dim3(256), 0, cur_stream(),
+                       X.data_ptr<double>(), yp, n, d, da, (int)tiles, per,
+                       ws.data_ptr<double>());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  hipLaunchKernelGGL(moments_reduce_f64_kernel, dim3((unsigned)(tiles * 64)), dim3(256), 0,
+                     cur_stream(), ws.data_ptr<double>(), (int)tiles, (int)split, da,
+                     M.data_ptr<double>());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return M;
+}
+
 std::vector<torch::Tensor> knn_select(torch::Tensor Q, torch::Tensor I, int64_t k) {
   TORCH_CHECK(Q.is_cuda() && I.is_cuda());
   TORCH_CHECK(Q.dtype() == torch::kFloat32 && I.dtype() == torch::kFloat32);
@@ -5811,6 +6164,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("label_accumulate_inertia", &label_accumulate_inertia, "sorted per-center sum/count + sum (x - c)^2 in the same pass",
         py::arg("X"), py::arg("labels"), py::arg("C"), py::arg("vec") = LA_VEC_DEFAULT);
   m.def("gram_f32", &gram_f32, "A^T A via MFMA f32");
+  m.def("moments_f64", &moments_f64,
+        "[X | 1 | y]^T [X | 1 | y] in f64 on f64 MFMA: Gram, column sums, X^T y and the y moments in one pass",
+        py::arg("X"), py::arg("y") = py::none());
   m.def("softmax_residual_loss", &softmax_residual_loss, "fused softmax residual + loss");
   m.def("knn_select", &knn_select, "fused MFMA distance + in-LDS top-k");
   m.def("rf_histogram", &rf_histogram, "LDS-privatized RF split histograms");

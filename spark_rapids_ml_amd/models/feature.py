@@ -27,7 +27,7 @@ from ..params import (
     Param,
     TypeConverters,
 )
-from ..ops import gram, eigh_sym, sign_flip
+from ..ops import moments, eigh_sym, sign_flip
 from ..ops.linalg import cov_from_gram
 from ..utils import as_numpy
 
@@ -112,9 +112,8 @@ class PCA(_PCAParams, Estimator):
             Xt = ctx.device_tensor(X)
             buf = torch.zeros((d + 1, d), dtype=torch.float64, device=Xt.device)
             if Xt.shape[0] > 0:
-                g = gram(Xt)  # f32 MFMA on GPU
-                buf[:d] = g.to(torch.float64)
-                buf[d] = Xt.sum(dim=0).to(torch.float64)
+                # f32 rows: MFMA gram_kernel; f64 rows: one pass of moments_f64
+                buf[:d], buf[d] = moments(Xt)[:2]
         buf = comm.allreduce_t(buf)
         mean = buf[d] / pdesc.m
         cov = cov_from_gram(buf[:d], mean, pdesc.m, ddof=1)

@@ -42,7 +42,7 @@ from ..params import (
     TypeConverters,
     HasWeightCol,
 )
-from ..ops import gram
+from ..ops import moments
 from ..utils import as_numpy
 from .tree import _RandomForestEstimator, _RandomForestModel
 
@@ -199,11 +199,13 @@ class LinearRegression(_LinearRegressionParams, Estimator):
             yt = to_device_tensor(np.ascontiguousarray(y), ctx.device).to(Xt.dtype)
             buf = torch.zeros((d + 3, w), dtype=torch.float64, device=Xt.device)
             if Xt.shape[0] > 0:
-                buf[:d, :d] = gram(Xt).to(torch.float64)
-                buf[d, :d] = (Xt.T @ yt).to(torch.float64)
-                buf[d + 1, :d] = Xt.sum(dim=0).to(torch.float64)
-                buf[d + 2, 0] = yt.sum().to(torch.float64)
-                buf[d + 2, 1] = (yt * yt).sum().to(torch.float64)
+                # f64 rows on the GPU: one pass of the moments_f64 kernel
+                G, xsum, Xty, ysum, y2sum = moments(Xt, yt)
+                buf[:d, :d] = G
+                buf[d, :d] = Xty
+                buf[d + 1, :d] = xsum
+                buf[d + 2, 0] = ysum
+                buf[d + 2, 1] = y2sum
         buf = comm.allreduce_t(buf)
         m = {
             "G": buf[:d, :d],

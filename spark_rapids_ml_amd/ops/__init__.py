@@ -13,7 +13,7 @@ missing extension raises instead of silently falling back to eager torch
 from .dispatch import has_hip_ops, hip_ops, require_hip_ops, use_hip
 from . import torch_ref
 from .kmeans import kmeans_assign_reduce, kmeans_predict
-from .linalg import gram, xty_gram, eigh_sym, sign_flip
+from .linalg import gram, moments, xty_gram, eigh_sym, sign_flip
 from .glm import logistic_grad_loss, linear_grad_loss
 from .knn import knn_topk
 from .forest import forest_backend, forest_predict, forest_traverse
@@ -27,6 +27,7 @@ __all__ = [
     "kmeans_assign_reduce",
     "kmeans_predict",
     "gram",
+    "moments",
     "xty_gram",
     "eigh_sym",
     "sign_flip",

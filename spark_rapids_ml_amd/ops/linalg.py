@@ -9,7 +9,8 @@ eigenvector sign convention is reproduced by `sign_flip`.
 
 from __future__ import annotations
 
-from typing import Tuple
+import os
+from typing import Optional, Tuple
 
 import torch
 
@@ -31,6 +32,40 @@ def gram(X: torch.Tensor) -> torch.Tensor:
 def xty_gram(X: torch.Tensor, y: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     """(X^T X, X^T y): the Gram rides the MFMA kernel, X^T y is a GEMV."""
     return gram(X), torch_ref.xty(X, y)
+
+
+def moments(
+    X: torch.Tensor, y: Optional[torch.Tensor] = None
+) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor], Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """(XᵀX [d,d], column sums [d], Xᵀy [d], Σy, Σy²) as f64 tensors on X's
+    device, the last three None without y: the moment set PCA and linear
+    regression fit from. f64 rows on gfx950 take one pass of the
+    `moments_f64` kernel (f64 MFMA over the upper-triangle tiles of
+    [X | 1 | y]ᵀ[X | 1 | y], no floating atomics, bitwise repeatable);
+    SRML_MOMENTS_F64=0 turns that off. Everything else (f32 rows, CPU) runs
+    the separate Gram, sum and GEMV expressions."""
+    if (
+        X.dtype == torch.float64
+        and use_hip(X)
+        and os.environ.get("SRML_MOMENTS_F64") != "0"
+    ):
+        d = X.shape[1]
+        yd = None if y is None else y.to(torch.float64).contiguous()
+        M = hip_ops().moments_f64(X.contiguous(), yd)
+        if y is None:
+            return M[:d, :d], M[:d, d], None, None, None
+        return M[:d, :d], M[:d, d], M[:d, d + 1], M[d, d + 1], M[d + 1, d + 1]
+    G = gram(X).to(torch.float64)
+    xsum = X.sum(dim=0).to(torch.float64)
+    if y is None:
+        return G, xsum, None, None, None
+    return (
+        G,
+        xsum,
+        (X.T @ y).to(torch.float64),
+        y.sum().to(torch.float64),
+        (y * y).sum().to(torch.float64),
+    )
 
 
 def eigh_sym(A: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:

@@ -97,7 +97,7 @@ def streamed_moments(
     xsum [d], and with y also Xty [d], ysum, y2sum (the moment set PCA and
     linear regression fit from; reference PCAMG / LinearRegressionMG
     partials)."""
-    from .ops import gram
+    from .ops import moments
 
     d = X.shape[1]
     G = torch.zeros((d, d), dtype=torch.float64, device=device)
@@ -106,11 +106,14 @@ def streamed_moments(
     ysum = torch.zeros((), dtype=torch.float64, device=device)
     y2sum = torch.zeros((), dtype=torch.float64, device=device)
     for s, e, Xc in iter_device_chunks(X, device, cap_bytes):
-        G += gram(Xc).to(torch.float64)
-        xsum += Xc.sum(dim=0).to(torch.float64)
+        yc = None
         if y is not None:
             yc = torch.from_numpy(np.ascontiguousarray(y[s:e])).to(device).to(Xc.dtype)
-            Xty += (Xc.T @ yc).to(torch.float64)
-            ysum += yc.sum().to(torch.float64)
-            y2sum += (yc * yc).sum().to(torch.float64)
+        g, xs, xy, ys, y2 = moments(Xc, yc)
+        G += g
+        xsum += xs
+        if y is not None:
+            Xty += xy
+            ysum += ys
+            y2sum += y2
     return {"G": G, "xsum": xsum, "Xty": Xty, "ysum": ysum, "y2sum": y2sum}
