@@ -1562,6 +1562,450 @@ __global__ __launch_bounds__(256) void moments_reduce_f64_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// logreg_grad_loss_f64: loss and gradient of the (multinomial or binary)
+// logistic objective for f64 rows, f64 from end to end on
+// v_mfma_f64_16x16x4_f64 (lane layout above kmeans_assign_f64_kernel). W is
+// [C, d (+ 1)] with the intercept in column d; it meets an implicit ones
+// column of X that the loads make (column == d gives 1.0), so no augmented
+// copy of X exists. Classes are padded to Cp = 16 * CT, CT in {1, 2, 4}. The
+// gradient's Cp x d accumulators cannot persist in one block for every d and
+// the softmax needs a row's whole d first, so X is read twice:
+//
+// 1. logreg_scores_f64_kernel: S = [X | 1] W^T, softmax (sigmoid for C == 1),
+//    residual R [n, Cp] (pad classes 0) and one loss partial per block. A
+//    block owns 128 rows and loops over the columns in panels of LG_BK = 32;
+//    a wave owns 32 rows as 2 x CT tiles (8 * CT accumulator doubles a lane).
+//    Layout: the A operand wants A[i = l & 15][k = l >> 4], rows across lanes,
+//    which in global memory is a stride of d; so panels go through LDS. They
+//    are staged row-major, lds_x[row][k], exactly as they lie in memory (64
+//    lanes write 4 rows x 256 B as double2 when d is even and X is 16-byte
+//    aligned, VEC; 2 rows x 256 B as doubles otherwise), and the transposition
+//    is the operand read lds_x[row0 + (l & 15)][4 kk + (l >> 4)]. W's panel
+//    [Cp][32] is staged the same way and read the same way as the B operand
+//    (B[k][j] = W[j][k]). Banks: a double covers two 4-byte banks, 32 double
+//    slots, and a 64-lane b64 read takes two passes of 32 lanes. The row
+//    stride is LG_LD = 34 doubles, 34 mod 32 = 2: the 16 rows of lanes 0..15
+//    (k = 4 kk) fall on the even slots, those of lanes 16..31 (k = 4 kk + 1)
+//    on the odd ones, so a pass touches every slot once; lanes 32..63
+//    likewise. (A stride of 32 would put all 16 rows on one slot; 33 gives
+//    2-way conflicts between the two k and misaligns the double2 writes.) The
+//    staging writes are contiguous along a row: conflict-free, and rows stay
+//    16-byte aligned (34 * 8 = 16 * 17).
+//    Pipeline: one LDS buffer with the write-after-barrier register pipeline
+//    of kmeans_assign_kernel; the loads of panel s + 2 are in flight during
+//    the MFMA phase of panel s + 1. The kernel is bound by its X reads (at
+//    Cp = 16 one MFMA consumes 512 B of X), so the block is kept light enough
+//    for several blocks per CU to have loads in flight.
+//    Epilogue in registers: in the C/D layout (row = 4 reg + (lane >> 4),
+//    class = 16 t + (lane & 15)) a row's classes lie across 16 lanes and the
+//    CT tiles of a lane; max and sum are xor-shuffles over offsets 1..8, which
+//    leave the same bits in all 16 lanes. Pad classes enter as -inf and 0.
+//    f64 exp/log/log1p, a true divide; C == 1 uses e = exp(-|z|), p = 1/(1+e)
+//    or e/(1+e), loss = max(-t z, 0) + log1p(e).
+// 2. logreg_grad_f64_kernel: G = R^T [X | 1], a TN product over rows. Work is
+//    split per wave, not per block: wave item = (row slice, 64-column stripe),
+//    stripe fastest, so the waves of a block walk the same rows and share R in
+//    L1. Accumulators: Cp x 64 a wave, 16 * CT doubles a lane. Both operands
+//    are loaded straight from global memory into the lane that feeds them to
+//    the MFMA: B[k = l >> 4][j = l & 15] = X[row0 + k][col(j)] is 16 lanes on
+//    128 contiguous bytes of a row (256 with VEC, where a lane's double2
+//    feeds two tiles whose columns interleave: col = c0 + 2 j + h), and
+//    A[i][k] = R[row0 + k][16 t + i] likewise. Every X element is used by one
+//    lane only, CT times from its register, so LDS staging would add a write,
+//    a read and a barrier and save no traffic; R is shared by the stripes
+//    through the caches (Cp / 64 of the X bytes per stripe). Pipeline: two
+//    register batches of LG_U k-steps (4 rows each); the loads of one batch
+//    are in flight during the MFMAs of the other.
+//    Each item writes its Cp x 64 partial to ws[slice][Cp][stripes * 64];
+//    logreg_reduce_f64_kernel adds the slices in slice order (compensated)
+//    into grad [C, d (+ 1)] and, in its last block, the loss partials in a
+//    fixed order. No floating atomics anywhere; the slice count depends on
+//    (n, d, Cp) alone, so the bits repeat from run to run.
+//
+// As compiled (ROCm 7.2 clang, -O3, -Rpass-analysis=kernel-resource-usage):
+// no kernel uses scratch or spills. logreg_scores_f64_kernel<CT, VEC>:
+// <1,true> 108 VGPR + 16 AGPR, 39,200 B LDS, 4 waves/SIMD; <1,false> 132 + 16,
+// 3; <2,true> 136 + 32, 43,552 B, 3; <2,false> 160 + 32, 2; <4,true> 190 + 64,
+// 52,256 B, 2; <4,false> 212 + 64, 1. logreg_grad_f64_kernel<CT, *>: <1> 250
+// VGPR + 64 AGPR, <2> 224 + 128, <4> 196 + 256; no LDS, 1 wave/SIMD: the two
+// register batches are its loads in flight (40 KB a wave at CT = 1).
+// logreg_reduce_f64_kernel: 18 VGPR, 2,048 B LDS, 8 waves/SIMD.
+// ---------------------------------------------------------------------------
+
+constexpr int LG_BM = 128;                       // rows per block (scores)
+constexpr int LG_BK = 32;                        // columns per panel
+constexpr int LG_LD = LG_BK + 2;                 // LDS row stride in doubles
+constexpr int LG_SX = LG_BM * LG_BK / 256;       // staged X doubles per thread (16)
+
+// rows i0 .. i0 + 128, columns k0 .. k0 + 32 of [X | 1] into registers
+template <bool VEC>
+__device__ __forceinline__ void lg_load_x(const double* __restrict__ X, int64_t n, int d,
+                                          int ka, int64_t i0, int k0, int tid,
+                                          double (&rg)[LG_SX]) {
+  const bool fast = (i0 + LG_BM <= n) && (k0 + LG_BK <= d);
+  if constexpr (VEC) {
+#pragma unroll
+    for (int q = 0; q < LG_SX / 2; ++q) {
+      const int e = q * 256 + tid;
+      const int64_t gr = i0 + (e >> 4);
+      const int gk = k0 + 2 * (e & 15);  // even, as d is: the pair never straddles d
+      double v0 = 0.0, v1 = 0.0;
+      if (fast || (gr < n && gk < d)) {
+        const double2 p = *reinterpret_cast<const double2*>(X + gr * (int64_t)d + gk);
+        v0 = p.x;
+        v1 = p.y;
+      } else if (gr < n && gk < ka) {
+        v0 = 1.0;  // gk == d: the ones column
+      }
+      rg[2 * q] = v0;
+      rg[2 * q + 1] = v1;
+    }
+  } else {
+#pragma unroll
+    for (int q = 0; q < LG_SX; ++q) {
+      const int e = q * 256 + tid;
+      const int64_t gr = i0 + (e >> 5);
+      const int gk = k0 + (e & 31);
+      double v = 0.0;
+      if (fast || (gr < n && gk < d)) v = X[gr * (int64_t)d + gk];
+      else if (gr < n && gk < ka) v = 1.0;
+      rg[q] = v;
+    }
+  }
+}
+
+template <bool VEC>
+__device__ __forceinline__ void lg_write_x(double (*lds)[LG_LD], int tid,
+                                           const double (&rg)[LG_SX]) {
+  if constexpr (VEC) {
+#pragma unroll
+    for (int q = 0; q < LG_SX / 2; ++q) {
+      const int e = q * 256 + tid;
+      *reinterpret_cast<double2*>(&lds[e >> 4][2 * (e & 15)]) =
+          make_double2(rg[2 * q], rg[2 * q + 1]);
+    }
+  } else {
+#pragma unroll
+    for (int q = 0; q < LG_SX; ++q) {
+      const int e = q * 256 + tid;
+      lds[e >> 5][e & 31] = rg[q];
+    }
+  }
+}
+
+// classes 0 .. 16 CT, columns k0 .. k0 + 32 of W (ka columns a row)
+template <int CT>
+__device__ __forceinline__ void lg_load_w(const double* __restrict__ W, int C, int ka, int k0,
+                                          int tid, double (&rg)[2 * CT]) {
+#pragma unroll
+  for (int q = 0; q < 2 * CT; ++q) {
+    const int e = q * 256 + tid;
+    const int c = e >> 5;
+    const int gk = k0 + (e & 31);
+    rg[q] = (c < C && gk < ka) ? W[(int64_t)c * ka + gk] : 0.0;
+  }
+}
+
+template <int CT>
+__device__ __forceinline__ void lg_write_w(double (*lds)[LG_LD], int tid,
+                                           const double (&rg)[2 * CT]) {
+#pragma unroll
+  for (int q = 0; q < 2 * CT; ++q) {
+    const int e = q * 256 + tid;
+    lds[e >> 5][e & 31] = rg[q];
+  }
+}
+
+template <int CT, bool VEC>
+__global__ __launch_bounds__(256) void logreg_scores_f64_kernel(
+    const double* __restrict__ X,   // [n, d] row-major
+    const int64_t* __restrict__ y,  // [n] class index (0/1 for C == 1)
+    const double* __restrict__ W,   // [C, ka] row-major, ka = d (+ 1)
+    int64_t n, int d, int ka, int C,
+    double* __restrict__ R,         // [n, 16 CT] residual, pad classes 0
+    double* __restrict__ partials) {  // [grid] loss of this block's rows
+  constexpr int Cp = 16 * CT;
+  __shared__ __attribute__((aligned(16))) double lds_x[LG_BM][LG_LD];
+  __shared__ __attribute__((aligned(16))) double lds_w[Cp][LG_LD];
+  __shared__ double block_loss[4];
+
+  const int64_t i0 = (int64_t)blockIdx.x * LG_BM;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const int l16 = lane & 15;
+  const int lk = lane >> 4;
+  const int nsteps = (ka + LG_BK - 1) / LG_BK;
+
+  f64x4 acc[2][CT];
+#pragma unroll
+  for (int m = 0; m < 2; ++m)
+#pragma unroll
+    for (int t = 0; t < CT; ++t)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) acc[m][t][r] = 0.0;
+
+  double rx[LG_SX], rw[2 * CT];
+  lg_load_x<VEC>(X, n, d, ka, i0, 0, tid, rx);
+  lg_load_w<CT>(W, C, ka, 0, tid, rw);
+  lg_write_x<VEC>(lds_x, tid, rx);
+  lg_write_w<CT>(lds_w, tid, rw);
+  if (nsteps > 1) {
+    lg_load_x<VEC>(X, n, d, ka, i0, LG_BK, tid, rx);
+    lg_load_w<CT>(W, C, ka, LG_BK, tid, rw);
+  }
+  __syncthreads();
+
+  for (int step = 0; step < nsteps; ++step) {
+#pragma unroll
+    for (int kk = 0; kk < LG_BK / 4; ++kk) {
+      const int kc = 4 * kk + lk;
+      double a[2], b[CT];
+#pragma unroll
+      for (int m = 0; m < 2; ++m) a[m] = lds_x[wave * 32 + m * 16 + l16][kc];
+#pragma unroll
+      for (int t = 0; t < CT; ++t) b[t] = lds_w[t * 16 + l16][kc];
+#pragma unroll
+      for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int t = 0; t < CT; ++t)
+          acc[m][t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[m], b[t], acc[m][t], 0, 0, 0);
+    }
+    __syncthreads();  // all waves done reading this panel
+    if (step + 1 < nsteps) {
+      lg_write_x<VEC>(lds_x, tid, rx);  // vmcnt-waits for loads issued a full phase ago
+      lg_write_w<CT>(lds_w, tid, rw);
+      if (step + 2 < nsteps) {
+        lg_load_x<VEC>(X, n, d, ka, i0, (step + 2) * LG_BK, tid, rx);
+        lg_load_w<CT>(W, C, ka, (step + 2) * LG_BK, tid, rw);
+      }
+      __syncthreads();
+    }
+  }
+
+  // epilogue: row wave*32 + m*16 + 4r + lk, class 16t + l16
+  double lloss = 0.0;
+#pragma unroll
+  for (int m = 0; m < 2; ++m)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int64_t gi = i0 + wave * 32 + m * 16 + 4 * r + lk;
+      const bool live = gi < n;
+      const int yi = live ? (int)y[gi] : -1;
+      if (C == 1) {
+        const double z = acc[m][0][r];
+        const double e = exp(-fabs(z));
+        const double p = (z >= 0.0) ? 1.0 / (1.0 + e) : e / (1.0 + e);
+        if (live) {
+          const double mz = yi ? -z : z;  // -t z, t = +-1
+          if (l16 == 0) lloss += fmax(mz, 0.0) + log1p(e);
+          R[gi * Cp + l16] = (l16 == 0) ? p - (double)yi : 0.0;
+        }
+      } else {
+        double s[CT], ex[CT];
+        double mx = -INFINITY;
+#pragma unroll
+        for (int t = 0; t < CT; ++t) {
+          s[t] = (t * 16 + l16 < C) ? acc[m][t][r] : -INFINITY;
+          mx = fmax(mx, s[t]);
+        }
+#pragma unroll
+        for (int off = 1; off < 16; off <<= 1) mx = fmax(mx, __shfl_xor(mx, off, 64));
+        double sum = 0.0;
+#pragma unroll
+        for (int t = 0; t < CT; ++t) {
+          ex[t] = (t * 16 + l16 < C) ? exp(s[t] - mx) : 0.0;
+          sum += ex[t];
+        }
+#pragma unroll
+        for (int off = 1; off < 16; off <<= 1) sum += __shfl_xor(sum, off, 64);
+        if (live) {
+#pragma unroll
+          for (int t = 0; t < CT; ++t) {
+            const int cls = t * 16 + l16;
+            const bool own = (cls == yi);
+            if (own) lloss += log(sum) - (s[t] - mx);
+            R[gi * Cp + cls] = (cls < C) ? ex[t] / sum - (own ? 1.0 : 0.0) : 0.0;
+          }
+        }
+      }
+    }
+  // fixed-order block sum: shuffle tree per wave, then the four waves in order
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) lloss += __shfl_down(lloss, off, 64);
+  if (lane == 0) block_loss[wave] = lloss;
+  __syncthreads();
+  if (tid == 0)
+    partials[blockIdx.x] = ((block_loss[0] + block_loss[1]) + block_loss[2]) + block_loss[3];
+}
+
+// k-steps (4 rows each) per register batch of the gradient kernel
+template <int CT>
+struct lg_u { static constexpr int value = (CT == 4) ? 4 : 8; };
+
+template <int CT, bool VEC>
+__global__ __launch_bounds__(256) void logreg_grad_f64_kernel(
+    const double* __restrict__ X,  // [n, d] row-major
+    const double* __restrict__ R,  // [n, 16 CT]
+    int64_t n, int d, int ka,
+    int ns64,                      // 64-column stripes of [X | 1]
+    int64_t per,                   // rows per slice, a multiple of the batch
+    int64_t items,                 // slices * ns64 wave items
+    double* __restrict__ ws) {     // [slices][16 CT][ns64 * 64]
+  constexpr int Cp = 16 * CT;
+  constexpr int U = lg_u<CT>::value;
+  const int lane = threadIdx.x & 63;
+  const int l16 = lane & 15;
+  const int lk = lane >> 4;
+  const int64_t item = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (item >= items) return;  // whole waves; the kernel has no barrier
+  const int stripe = (int)(item % ns64);
+  const int64_t slice = item / ns64;
+  const int col0 = stripe * 64;
+  const int64_t r_begin = min(n, slice * per);
+  const int64_t r_end = min(n, r_begin + per);
+
+  // this lane's column of pair-tile p, half h
+  int cj[2][2];
+#pragma unroll
+  for (int p = 0; p < 2; ++p)
+#pragma unroll
+    for (int h = 0; h < 2; ++h) cj[p][h] = col0 + 32 * p + (VEC ? 2 * l16 + h : 16 * h + l16);
+  const int plive = (col0 + 32 < ka) ? 2 : 1;  // pair-tiles with a column below ka
+  const bool colfast = (col0 + 64 <= d);
+
+  f64x4 acc[CT][2][2];
+#pragma unroll
+  for (int t = 0; t < CT; ++t)
+#pragma unroll
+    for (int p = 0; p < 2; ++p)
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[t][p][h][r] = 0.0;
+
+  double xa[U][2][2], ra[U][CT], xb[U][2][2], rb[U][CT];
+
+#define LG_LOAD(r0, xx, rr)                                                            \
+  do {                                                                                 \
+    if (colfast && (r0) + 4 * U <= r_end) {                                            \
+      _Pragma("unroll") for (int u = 0; u < U; ++u) {                                  \
+        const int64_t row = (r0) + 4 * u + lk;                                         \
+        const double* __restrict__ xr = X + row * (int64_t)d;                          \
+        _Pragma("unroll") for (int p = 0; p < 2; ++p) {                                \
+          if constexpr (VEC) {                                                         \
+            const double2 v = *reinterpret_cast<const double2*>(xr + cj[p][0]);        \
+            xx[u][p][0] = v.x;                                                         \
+            xx[u][p][1] = v.y;                                                         \
+          } else {                                                                     \
+            xx[u][p][0] = xr[cj[p][0]];                                                \
+            xx[u][p][1] = xr[cj[p][1]];                                                \
+          }                                                                            \
+        }                                                                              \
+        _Pragma("unroll") for (int t = 0; t < CT; ++t)                                 \
+            rr[u][t] = R[row * Cp + t * 16 + l16];                                     \
+      }                                                                                \
+    } else {                                                                           \
+      _Pragma("unroll") for (int u = 0; u < U; ++u) {                                  \
+        const int64_t row = (r0) + 4 * u + lk;                                         \
+        const bool rlive = row < r_end;                                                \
+        _Pragma("unroll") for (int p = 0; p < 2; ++p)                                  \
+        _Pragma("unroll") for (int h = 0; h < 2; ++h) {                                \
+          const int c = cj[p][h];                                                      \
+          double v = 0.0;                                                              \
+          if (rlive && c < d) v = X[row * (int64_t)d + c];                             \
+          else if (rlive && c < ka) v = 1.0;                                           \
+          xx[u][p][h] = v;                                                             \
+        }                                                                              \
+        _Pragma("unroll") for (int t = 0; t < CT; ++t)                                 \
+            rr[u][t] = rlive ? R[row * Cp + t * 16 + l16] : 0.0;                       \
+      }                                                                                \
+    }                                                                                  \
+  } while (0)
+
+#define LG_MFMA(xx, rr)                                                                \
+  do {                                                                                 \
+    _Pragma("unroll") for (int u = 0; u < U; ++u)                                      \
+    _Pragma("unroll") for (int t = 0; t < CT; ++t)                                     \
+    _Pragma("unroll") for (int p = 0; p < 2; ++p)                                      \
+      if (p < plive) {                                                                 \
+        _Pragma("unroll") for (int h = 0; h < 2; ++h)                                  \
+          acc[t][p][h] = __builtin_amdgcn_mfma_f64_16x16x4f64(rr[u][t], xx[u][p][h],   \
+                                                              acc[t][p][h], 0, 0, 0);  \
+      }                                                                                \
+  } while (0)
+
+  if (r_begin < r_end) {
+    LG_LOAD(r_begin, xa, ra);
+    for (int64_t r0 = r_begin;;) {
+      r0 += 4 * U;
+      if (r0 < r_end) LG_LOAD(r0, xb, rb);  // in flight during the MFMAs of batch a
+      LG_MFMA(xa, ra);
+      if (r0 >= r_end) break;
+      r0 += 4 * U;
+      if (r0 < r_end) LG_LOAD(r0, xa, ra);
+      LG_MFMA(xb, rb);
+      if (r0 >= r_end) break;
+    }
+  }
+#undef LG_LOAD
+#undef LG_MFMA
+
+  // class 16t + 4r + lk, column cj[p][h]; an empty slice writes its zeros
+  const int kaP = ns64 * 64;
+  double* __restrict__ out = ws + slice * (int64_t)Cp * kaP;
+#pragma unroll
+  for (int t = 0; t < CT; ++t)
+#pragma unroll
+    for (int p = 0; p < 2; ++p)
+      if (p < plive) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+            out[(int64_t)(t * 16 + 4 * r + lk) * kaP + cj[p][h]] = acc[t][p][h][r];
+      }
+}
+
+// grad[c][j] = sum over slices, in slice order and compensated, of the
+// workspace partials: one thread per element. The block after the last adds
+// the loss partials: each thread its strided share in order, then a fixed tree.
+__global__ __launch_bounds__(256) void logreg_reduce_f64_kernel(
+    const double* __restrict__ ws, int64_t split, int Cp, int kaP, int C, int ka,
+    const double* __restrict__ partials, int64_t nparts,
+    double* __restrict__ grad,    // [C, ka]
+    double* __restrict__ loss) {  // [1]
+  __shared__ double red[256];
+  const int tid = threadIdx.x;
+  if (blockIdx.x + 1 == gridDim.x) {
+    double s = 0.0;
+    for (int64_t i = tid; i < nparts; i += 256) s += partials[i];
+    red[tid] = s;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+      if (tid < w) red[tid] += red[tid + w];
+      __syncthreads();
+    }
+    if (tid == 0) loss[0] = red[0];
+    return;
+  }
+  const int64_t idx = (int64_t)blockIdx.x * 256 + tid;
+  if (idx >= (int64_t)C * ka) return;
+  const int c = (int)(idx / ka), j = (int)(idx % ka);
+  const double* p = ws + (int64_t)c * kaP + j;
+  const int64_t stride = (int64_t)Cp * kaP;
+  double s = p[0], cc = 0.0;  // Neumaier, as moments_reduce_f64_kernel
+#pragma unroll 8  // the loads do not depend on the sum: eight in flight, same order
+  for (int64_t sp = 1; sp < split; ++sp) {
+    const double v = p[sp * stride];
+    const double t = s + v;
+    cc += (fabs(s) >= fabs(v)) ? (s - t) + v : (v - t) + s;
+    s = t;
+  }
+  grad[idx] = s + cc;
+}
+
+// ---------------------------------------------------------------------------
 // knn_select: fused brute-force k-NN — MFMA distance tiles + in-LDS
 // per-query top-k (reference NearestNeighborsMG's tiled ||x-y||^2 + top-k
 // merge, SURVEY.md §2.3b knn.py:763-774). No [nq, ni] distance matrix is
@@ -5093,6 +5537,86 @@ torch::Tensor moments_f64(torch::Tensor X, c10::optional<torch::Tensor> y) {
   return M;
 }
 
+// Row split of logreg_grad_f64_kernel for (n, d (+ 1), Cp): about 4096 wave
+// items (16 waves per CU of a 256-CU part) over stripes x slices, no slice
+// shorter than two register batches, slices a whole number of batches, and no
+// empty slice. A function of the shape alone, so the summation order never
+// depends on the device. Returns rows per slice; the split follows.
+static inline int64_t logreg_f64_rows_per_slice(int64_t n, int64_t ka, int64_t ct) {
+  const int64_t batch = 4 * (ct == 4 ? 4 : 8);
+  const int64_t ns64 = (ka + 63) / 64;
+  const int64_t nb = (n + batch - 1) / batch;
+  const int64_t want = std::max<int64_t>(1, std::min<int64_t>(4096 / ns64, nb / 2));
+  return (nb + want - 1) / want * batch;
+}
+
+template <int CT, bool VEC>
+static void logreg_f64_launch(const double* X, const int64_t* y, const double* W, int64_t n,
+                              int d, int ka, int C, double* R, double* partials,
+                              int64_t nblocks, int ns64, int64_t per, int64_t split,
+                              double* ws, double* grad, double* loss) {
+  hipLaunchKernelGGL((logreg_scores_f64_kernel<CT, VEC>), dim3((unsigned)nblocks), dim3(256), 0,
+                     cur_stream(), X, y, W, n, d, ka, C, R, partials);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  const int64_t items = split * ns64;
+  hipLaunchKernelGGL((logreg_grad_f64_kernel<CT, VEC>), dim3((unsigned)((items + 3) / 4)),
+                     dim3(256), 0, cur_stream(), X, R, n, d, ka, ns64, per, items, ws);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  const int64_t gblocks = ((int64_t)C * ka + 255) / 256 + 1;
+  hipLaunchKernelGGL(logreg_reduce_f64_kernel, dim3((unsigned)gblocks), dim3(256), 0,
+                     cur_stream(), ws, split, 16 * CT, ns64 * 64, C, ka, partials, nblocks,
+                     grad, loss);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+}
+
+// (grad [C, d (+ 1)], loss []) of the summed logistic loss over the rows of X
+// for W [C, d (+ 1)] (intercept last): softmax over C classes, sigmoid for
+// C == 1. Any n >= 0, d >= 1, 1 <= C <= 64; n == 0 returns zeros without a
+// launch.
+std::vector<torch::Tensor> logreg_grad_loss_f64(torch::Tensor X, torch::Tensor y,
+                                                torch::Tensor W, bool fit_intercept) {
+  TORCH_CHECK(X.is_cuda() && X.dtype() == torch::kFloat64 && X.dim() == 2 && X.is_contiguous(),
+              "logreg_grad_loss_f64 takes a contiguous f64 [n, d] device X");
+  const int64_t n = X.size(0);
+  const int64_t d64 = X.size(1);
+  TORCH_CHECK(d64 >= 1 && d64 < (int64_t(1) << 31) - 256, "d out of range");
+  const int d = (int)d64;
+  const int ka = d + (fit_intercept ? 1 : 0);
+  TORCH_CHECK(y.is_cuda() && y.dtype() == torch::kInt64 && y.dim() == 1 && y.is_contiguous() &&
+                  y.numel() == n,
+              "y must be a contiguous int64 [n] device tensor");
+  TORCH_CHECK(W.is_cuda() && W.dtype() == torch::kFloat64 && W.dim() == 2 && W.is_contiguous() &&
+                  W.size(1) == ka,
+              "W must be a contiguous f64 [C, d (+ 1)] device tensor");
+  const int64_t C64 = W.size(0);
+  TORCH_CHECK(C64 >= 1 && C64 <= 64, "logreg_grad_loss_f64 serves 1 <= C <= 64");
+  const int C = (int)C64;
+  if (n == 0) return {torch::zeros({C64, (int64_t)ka}, X.options()), torch::zeros({}, X.options())};
+  const int ct = C <= 16 ? 1 : (C <= 32 ? 2 : 4);
+  const int64_t nblocks = (n + LG_BM - 1) / LG_BM;
+  const int64_t ns64 = (ka + 63) / 64;
+  const int64_t per = logreg_f64_rows_per_slice(n, ka, ct);
+  const int64_t split = (n + per - 1) / per;
+  TORCH_CHECK(nblocks < (int64_t(1) << 31) && split * ns64 < (int64_t(1) << 31), "too many blocks");
+  auto R = torch::empty({n, (int64_t)16 * ct}, X.options());
+  auto partials = torch::empty({nblocks}, X.options());
+  auto ws = torch::empty({split, (int64_t)16 * ct, ns64 * 64}, X.options());
+  auto grad = torch::empty({C64, (int64_t)ka}, X.options());
+  auto loss = torch::empty({1}, X.options());
+  const bool vec = d % 2 == 0 && (uintptr_t)X.data_ptr() % 16 == 0;
+#define LG_GO(CT, VEC)                                                                      \
+  logreg_f64_launch<CT, VEC>(X.data_ptr<double>(), y.data_ptr<int64_t>(),                   \
+                             W.data_ptr<double>(), n, d, ka, C, R.data_ptr<double>(),       \
+                             partials.data_ptr<double>(), nblocks, (int)ns64, per, split,   \
+                             ws.data_ptr<double>(), grad.data_ptr<double>(),                \
+                             loss.data_ptr<double>())
+  if (ct == 1) { if (vec) LG_GO(1, true); else LG_GO(1, false); }
+  else if (ct == 2) { if (vec) LG_GO(2, true); else LG_GO(2, false); }
+  else { if (vec) LG_GO(4, true); else LG_GO(4, false); }
+#undef LG_GO
+  return {grad, loss.squeeze(0)};
+}
+
 std::vector<torch::Tensor> knn_select(torch::Tensor Q, torch::Tensor I, int64_t k) {
   TORCH_CHECK(Q.is_cuda() && I.is_cuda());
   TORCH_CHECK(Q.dtype() == torch::kFloat32 && I.dtype() == torch::kFloat32);
@@ -6167,6 +6691,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("moments_f64", &moments_f64,
         "[X | 1 | y]^T [X | 1 | y] in f64 on f64 MFMA: Gram, column sums, X^T y and the y moments in one pass",
         py::arg("X"), py::arg("y") = py::none());
+  m.def("logreg_grad_loss_f64", &logreg_grad_loss_f64,
+        "(grad, loss) of the logistic objective for f64 rows on f64 MFMA: scores + softmax "
+        "residual + loss in one pass, R^T [X | 1] in a second, fixed-order reduces");
   m.def("softmax_residual_loss", &softmax_residual_loss, "fused softmax residual + loss");
   m.def("knn_select", &knn_select, "fused MFMA distance + in-LDS top-k");
   m.def("rf_histogram", &rf_histogram, "LDS-privatized RF split histograms");

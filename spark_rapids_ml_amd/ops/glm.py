@@ -8,6 +8,7 @@ residual into a single elementwise kernel between them.
 
 from __future__ import annotations
 
+import os
 from typing import Optional, Tuple
 
 import torch
@@ -26,8 +27,10 @@ def logistic_grad_loss(
     """Local-shard gradient (sum, unscaled) and loss (sum) for binary
     (W: [1, d(+1)], sigmoid) or multinomial (W: [C, d(+1)], softmax).
 
-    Dense X runs the GEMMs on MFMA (hipBLASLt) with the fused HIP
-    softmax-residual kernel between them. Sparse CSR X (reference sparse
+    Dense f32 X runs the GEMMs on MFMA (hipBLASLt) with the fused HIP
+    softmax-residual kernel between them. Dense f64 X on the GPU with
+    C <= 64 runs `logreg_grad_loss_f64` (SRML_LOGREG_F64=0 turns that off;
+    then, and for C > 64, the f64 torch expressions run). Sparse CSR X (reference sparse
     path, classification.py:960-966) runs scores = X@Wᵀ and grad = (XᵀR)ᵀ
     through rocSPARSE SpMM; pass XT (the pre-transposed CSR) to avoid a
     transpose per iteration.
@@ -36,6 +39,18 @@ def logistic_grad_loss(
     n = X.shape[0]
     d = X.shape[1]
     C = W.shape[0]
+    f64_rows = not sparse and X.dtype == torch.float64 and use_hip(X)
+    if f64_rows and C <= 64 and os.environ.get("SRML_LOGREG_F64") != "0":
+        # f64 from end to end on the own f64 MFMA kernels: scores, softmax
+        # residual and loss in one pass over X, Rᵀ[X | 1] in a second; no
+        # floating atomics, bitwise repeatable
+        grad, loss = hip_ops().logreg_grad_loss_f64(
+            X.contiguous(),
+            y_idx.to(torch.int64).contiguous(),
+            W.to(torch.float64).contiguous(),
+            fit_intercept,
+        )
+        return grad, loss
     coef = W[:, :d]
     hip_csr = sparse and use_hip(W) and C <= 32 and W.dtype == torch.float32
     if hip_csr:
@@ -54,7 +69,11 @@ def logistic_grad_loss(
     if fit_intercept:
         scores = scores + W[:, d][None, :]
 
-    if use_hip(scores) and y_idx.dtype == torch.int64:
+    if f64_rows:
+        # outside the kernel's gate (C > 64, or SRML_LOGREG_F64=0) f64 rows
+        # stay f64: never through the f32 softmax kernel
+        resid, loss = torch_ref.softmax_residual(scores, y_idx)
+    elif use_hip(scores) and y_idx.dtype == torch.int64:
         ext = hip_ops()
         resid, loss = ext.softmax_residual_loss(
             scores.contiguous().to(torch.float32), y_idx.contiguous()
