@@ -5130,6 +5130,277 @@ __global__ __launch_bounds__(256) void fil_predict_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// rf_best_split_scan: split scan with lanes over BINS and classes streamed,
+// so no per-class registers: any C, criterion gini (0) or entropy (1).
+//
+// Both criteria are class-sums of one scalar function phi of a count:
+// phi(x) = x^2 (gini) or x*log2(x), phi(0) = 0 (entropy, in bits as Spark's
+// Entropy.calculate). With S_X = sum_c phi(X_c) for the left, right and total
+// class counts and l, r, t their row counts,
+//   gini:    gain = (S_L/l + S_R/r - S_T/t) / t      (the existing kernel's
+//            g_p - (l/t) g_l - (r/t) g_r with 1 - l/t - r/t = 0)
+//   entropy: gain = ([t log2 t - S_T] - [l log2 l - S_L] - [r log2 r - S_R]) / t
+// so a lane carries S_L, S_R and l for each of its boundaries, whatever C is.
+// The phi sums and the combination are f64: at a 2^23-row node n*log2(n) is
+// ~1.9e8, where an f32 ulp is 16, and the differences above would leave an
+// error of order 1e-6 in the gain. Counts are integers < 2^24, exact in f32.
+//
+// One block per node, 4 waves; wave w takes features w, w+4, ... For one
+// feature the [nb, C] slab is contiguous; the wave stages it in its own LDS
+// region one tile of TW = min(C, 16) classes at a time with coalesced loads
+// (float4 when the tile is the whole slab). Lane l owns the Q = ceil(nb/64)
+// consecutive bins l*Q .. l*Q+Q-1 (nb <= 256 -> Q <= 4). Per class a lane
+// sums its bins, one inclusive wave scan gives the prefix, lane 63 the total.
+// The tile is padded by one word per 64 (word a lives at a + a/64): lanes
+// that read one class of different bins are Q*TW words apart, and the pad
+// shifts each group of 64/(Q*TW) lanes to the next bank.
+// LDS per wave: nb*TW + nb*TW/64 + 1 words (16.3 KB at nb = 256, TW = 16),
+// plus 32 bytes per block for the reduce; checked on the host.
+//
+// Order of the argmax: lane's boundaries, wave max, the wave's running best
+// over its features, block max over the 4 waves — all on one packed key
+// (gain, then lowest feature, then lowest bin), so the result is a pure
+// function of H. The whole block then writes the winner's left/right counts.
+// ---------------------------------------------------------------------------
+
+constexpr int RSS_TW = 16;
+
+__host__ __device__ inline int rss_wave_words(int nb, int C) {
+  const int w = nb * (C < RSS_TW ? C : RSS_TW);
+  return w + w / 64 + 1;
+}
+
+template <int CRIT>
+__device__ inline double rss_phi(float x) {
+  if (CRIT == 0) return (double)x * (double)x;
+  return x > 0.0f ? (double)x * log2((double)x) : 0.0;
+}
+
+// float -> unsigned with the same order (negative gains of rounding size
+// included), and back
+__device__ inline unsigned rss_ord(float g) {
+  const unsigned u = __float_as_uint(g);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ inline float rss_unord(unsigned u) {
+  return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
+}
+
+template <int CRIT, int Q>
+__global__ __launch_bounds__(256) void rf_best_split_scan_kernel(
+    const float* __restrict__ H,  // [B, F, nb, C]
+    int F, int nb, int C, int min_leaf,
+    float* __restrict__ out_gain,   // [B]
+    int32_t* __restrict__ out_feat, // [B] (chunk-local feature idx)
+    int32_t* __restrict__ out_bin,  // [B]
+    float* __restrict__ out_lval,   // [B, C]
+    float* __restrict__ out_rval) { // [B, C]
+  extern __shared__ __attribute__((aligned(16))) float rss_lds[];
+  __shared__ unsigned long long red[4];
+  const int b = blockIdx.x;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const float* Hb = H + (int64_t)b * F * nb * C;
+  float* tile = rss_lds + (size_t)wave * rss_wave_words(nb, C);
+  const int bin0 = lane * Q;
+  // no valid boundary: gain -1, feature and bin fields 0 (decoded to -1)
+  const unsigned long long none = (unsigned long long)rss_ord(-1.0f) << 32;
+  unsigned long long best = none;
+
+  for (int f = wave; f < F; f += 4) {
+    const float* Hf = Hb + (int64_t)f * nb * C;
+    double sL[Q], sR[Q], lc[Q];
+#pragma unroll
+    for (int j = 0; j < Q; ++j) sL[j] = sR[j] = lc[j] = 0.0;
+    double sT = 0.0, t = 0.0;
+
+    for (int c0 = 0; c0 < C; c0 += RSS_TW) {
+      const int tw = min(RSS_TW, C - c0);
+      const int words = nb * tw;
+      cp_wave_sync();  // the previous tile's reads are done
+      if (tw == C && (words & 3) == 0) {
+        const float4* src = reinterpret_cast<const float4*>(Hf);
+        for (int e = lane; e < (words >> 2); e += 64) {
+          const float4 v = src[e];
+          const int a = e * 4;  // a .. a+3 share one 64-word group
+          float* dst = tile + a + (a >> 6);
+          dst[0] = v.x; dst[1] = v.y; dst[2] = v.z; dst[3] = v.w;
+        }
+      } else {
+        for (int e = lane; e < words; e += 64) {
+          const int bin = e / tw, cc = e - bin * tw;
+          tile[e + (e >> 6)] = Hf[(int64_t)bin * C + c0 + cc];
+        }
+      }
+      cp_wave_sync();
+
+      for (int cc = 0; cc < tw; ++cc) {
+        float v[Q];
+        float own = 0.0f;
+#pragma unroll
+        for (int j = 0; j < Q; ++j) {
+          const int a = (bin0 + j) * tw + cc;
+          v[j] = (bin0 + j < nb) ? tile[a + (a >> 6)] : 0.0f;
+          own += v[j];
+        }
+        float incl = own;  // inclusive scan over lanes
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+          const float o = __shfl_up(incl, off, 64);
+          if (lane >= off) incl += o;
+        }
+        const float T = __shfl(incl, 63, 64);
+        sT += rss_phi<CRIT>(T);
+        t += (double)T;
+        float run = incl - own;
+#pragma unroll
+        for (int j = 0; j < Q; ++j) {
+          run += v[j];
+          sL[j] += rss_phi<CRIT>(run);
+          sR[j] += rss_phi<CRIT>(T - run);
+          lc[j] += (double)run;
+        }
+      }
+    }
+
+    if (t < 2.0 * min_leaf) continue;  // wave-uniform
+    const double pT = (CRIT == 0) ? sT / t : t * log2(t) - sT;
+#pragma unroll
+    for (int j = 0; j < Q; ++j) {
+      const int bin = bin0 + j;
+      const double l = lc[j], r = t - l;
+      if (bin < nb - 1 && l >= min_leaf && r >= min_leaf && l > 0.0 && r > 0.0) {
+        double g;
+        if (CRIT == 0) g = (sL[j] / l + sR[j] / r - pT) / t;
+        else g = (pT - (l * log2(l) - sL[j]) - (r * log2(r) - sR[j])) / t;
+        const unsigned long long key =
+            ((unsigned long long)rss_ord((float)g) << 32) |
+            ((unsigned)(0xffff - f) << 16) | (unsigned)(0xffff - bin);
+        if (key > best) best = key;
+      }
+    }
+  }
+
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const unsigned long long o = __shfl_xor(best, off, 64);
+    if (o > best) best = o;
+  }
+  if (lane == 0) red[wave] = best;
+  __syncthreads();
+  unsigned long long m = red[0];
+  for (int w = 1; w < 4; ++w)
+    if (red[w] > m) m = red[w];
+  const bool found = m != none;
+  const int f = found ? 0xffff - (int)((m >> 16) & 0xffff) : -1;
+  const int bin = found ? 0xffff - (int)(m & 0xffff) : -1;
+  if (tid == 0) {
+    out_gain[b] = found ? rss_unord((unsigned)(m >> 32)) : -1.0f;
+    out_feat[b] = f;
+    out_bin[b] = bin;
+  }
+  const float* Hf = Hb + (int64_t)(found ? f : 0) * nb * C;
+  for (int c = tid; c < C; c += 256) {
+    float l = 0.0f, tot = 0.0f;
+    if (found) {
+      for (int bb = 0; bb < nb; ++bb) {
+        const float v = Hf[(int64_t)bb * C + c];
+        tot += v;
+        if (bb <= bin) l += v;
+      }
+    }
+    out_lval[(int64_t)b * C + c] = l;
+    out_rval[(int64_t)b * C + c] = tot - l;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// fil_predict_wide: classification inference for value widths past the 16
+// vote registers of fil_predict. One WAVE per row, 4 rows per block,
+// grid-stride over rows; per batch of up to 64 trees:
+//   walk: lane l walks tree batch*64 + l for the wave's row (all lanes read
+//         the same row: it is cached in the wave's LDS when d <= FW_DMAX) and
+//         ends with one leaf's arena index;
+//   vote: for j = 0 .. batch-1 in tree order lane j's leaf is broadcast, the
+//         lanes read value[leaf, lane + 64k] coalesced, the leaf sum s is
+//         reduced over the wave and v/s is added to the lane's accumulators.
+// Trees are added in the order 0 .. T-1, as the torch traversal adds them.
+// A lane holds FW_K = 4 accumulators (classes lane, lane+64, ...): vw <= 256,
+// checked on the host. Routing is the training rule: x < thr goes LEFT; a
+// root that is a leaf is walked in zero steps.
+// LDS per wave: d floats (d <= FW_DMAX = 4096: 16 KB), else none.
+// ---------------------------------------------------------------------------
+
+constexpr int FW_K = 4;
+constexpr int FW_DMAX = 4096;
+
+__global__ __launch_bounds__(256) void fil_predict_wide_kernel(
+    const float* __restrict__ X,        // [n, d]
+    const int32_t* __restrict__ feat,   // arena [total_nodes]
+    const float* __restrict__ thr,      // arena
+    const int32_t* __restrict__ left,   // arena (tree-local ids)
+    const int32_t* __restrict__ right,  // arena
+    const float* __restrict__ value,    // arena [total_nodes, vw]
+    const int64_t* __restrict__ roots,  // [T] arena offset of each tree root
+    int64_t n, int d, int T, int vw, int cache_row,
+    float* __restrict__ out) {          // [n, vw] summed votes
+  extern __shared__ __attribute__((aligned(16))) float fw_lds[];
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  float* xs = fw_lds + (size_t)wave * (cache_row ? d : 0);
+  const int64_t stride = (int64_t)gridDim.x * 4;
+  for (int64_t i = (int64_t)blockIdx.x * 4 + wave; i < n; i += stride) {
+    const float* xrow = X + i * d;
+    if (cache_row) {
+      cp_wave_sync();  // the previous row's walks are done
+      for (int e = lane; e < d; e += 64) xs[e] = xrow[e];
+      cp_wave_sync();
+    }
+    const float* xr = cache_row ? xs : xrow;
+    float acc[FW_K];
+#pragma unroll
+    for (int k = 0; k < FW_K; ++k) acc[k] = 0.0f;
+    for (int t0 = 0; t0 < T; t0 += 64) {
+      const int batch = min(64, T - t0);
+      int64_t leaf = 0;
+      if (lane < batch) {
+        const int64_t base = roots[t0 + lane];
+        int node = 0;
+        int f = feat[base];
+        while (f >= 0) {
+          node = (xr[f] < thr[base + node]) ? left[base + node] : right[base + node];
+          f = feat[base + node];
+        }
+        leaf = base + node;
+      }
+      for (int j = 0; j < batch; ++j) {
+        const float* v = value + __shfl(leaf, j, 64) * vw;
+        float vk[FW_K];
+        float s = 0.0f;
+#pragma unroll
+        for (int k = 0; k < FW_K; ++k) {
+          const int c = lane + 64 * k;
+          vk[k] = c < vw ? v[c] : 0.0f;
+          s += vk[k];
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+        // normalized class-count vote (matches the torch traversal)
+        s = fmaxf(s, 1e-12f);
+#pragma unroll
+        for (int k = 0; k < FW_K; ++k) acc[k] += vk[k] / s;
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < FW_K; ++k) {
+      const int c = lane + 64 * k;
+      if (c < vw) out[i * vw + c] = acc[k];
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // softmax_residual_loss: per-row softmax (C>1) or sigmoid (C==1) residual
 // and summed log-loss. resid = softmax(scores) - onehot(y) (or p - y).
 // One wave per row chunk; memory-bound, fused to one pass.
@@ -5777,6 +6048,53 @@ std::vector<torch::Tensor> rf_best_split(torch::Tensor H, int64_t min_leaf,
                        (int)min_leaf, classif ? 1 : 0, gain.data_ptr<float>(),
                        feat.data_ptr<int32_t>(), bin.data_ptr<int32_t>(),
                        lval.data_ptr<float>(), rval.data_ptr<float>());
+    C10_HIP_KERNEL_LAUNCH_CHECK();
+  }
+  return {gain, feat, bin, lval, rval};
+}
+
+template <int CRIT>
+static void rf_best_split_scan_launch(int Q, unsigned B, size_t lds, const float* H,
+                                      int F, int nb, int C, int min_leaf, float* gain,
+                                      int32_t* feat, int32_t* bin, float* lval,
+                                      float* rval) {
+#define RSS_CALL(QQ)                                                              \
+  hipLaunchKernelGGL((rf_best_split_scan_kernel<CRIT, QQ>), dim3(B), dim3(256),   \
+                     lds, cur_stream(), H, F, nb, C, min_leaf, gain, feat, bin,   \
+                     lval, rval)
+  if (Q == 1) RSS_CALL(1);
+  else if (Q == 2) RSS_CALL(2);
+  else if (Q == 3) RSS_CALL(3);
+  else RSS_CALL(4);
+#undef RSS_CALL
+}
+
+std::vector<torch::Tensor> rf_best_split_scan(torch::Tensor H, int64_t min_leaf,
+                                               int64_t criterion) {
+  TORCH_CHECK(H.is_cuda() && H.dtype() == torch::kFloat32 && H.is_contiguous());
+  TORCH_CHECK(H.dim() == 4, "rf_best_split_scan: H is [B, F, nb, C]");
+  TORCH_CHECK(criterion == 0 || criterion == 1,
+              "rf_best_split_scan: criterion is 0 (gini) or 1 (entropy)");
+  const int B = (int)H.size(0);
+  const int F = (int)H.size(1);
+  const int nb = (int)H.size(2);
+  const int C = (int)H.size(3);
+  TORCH_CHECK(nb >= 1 && nb <= 256, "rf_best_split_scan supports 1 <= n_bins <= 256");
+  TORCH_CHECK(C >= 1 && F < 0xffff);
+  const size_t lds = (size_t)4 * rss_wave_words(nb, C) * sizeof(float);
+  TORCH_CHECK(lds + 32 <= 160 * 1024, "rf_best_split_scan: tile too large for LDS");
+  auto gain = torch::empty({B}, H.options());
+  auto feat = torch::empty({B}, H.options().dtype(torch::kInt32));
+  auto bin = torch::empty({B}, H.options().dtype(torch::kInt32));
+  auto lval = torch::empty({B, C}, H.options());
+  auto rval = torch::empty({B, C}, H.options());
+  if (B > 0) {
+    const int Q = (nb + 63) / 64;
+    auto launch = criterion == 0 ? rf_best_split_scan_launch<0>
+                                 : rf_best_split_scan_launch<1>;
+    launch(Q, (unsigned)B, lds, H.data_ptr<float>(), F, nb, C, (int)min_leaf,
+           gain.data_ptr<float>(), feat.data_ptr<int32_t>(), bin.data_ptr<int32_t>(),
+           lval.data_ptr<float>(), rval.data_ptr<float>());
     C10_HIP_KERNEL_LAUNCH_CHECK();
   }
   return {gain, feat, bin, lval, rval};
@@ -6590,6 +6908,36 @@ torch::Tensor fil_predict(torch::Tensor X, torch::Tensor feat, torch::Tensor thr
   return out;
 }
 
+torch::Tensor fil_predict_wide(torch::Tensor X, torch::Tensor feat, torch::Tensor thr,
+                               torch::Tensor left, torch::Tensor right,
+                               torch::Tensor value, torch::Tensor roots) {
+  TORCH_CHECK(X.is_cuda() && X.dtype() == torch::kFloat32 && X.is_contiguous());
+  TORCH_CHECK(feat.dtype() == torch::kInt32 && left.dtype() == torch::kInt32 &&
+              right.dtype() == torch::kInt32 && thr.dtype() == torch::kFloat32 &&
+              value.dtype() == torch::kFloat32 && roots.dtype() == torch::kInt64);
+  TORCH_CHECK(value.dim() == 2 && value.is_contiguous());
+  const int64_t n = X.size(0);
+  const int d = (int)X.size(1);
+  const int T = (int)roots.size(0);
+  const int vw = (int)value.size(1);
+  TORCH_CHECK(vw >= 1 && vw <= 64 * FW_K, "fil_predict_wide supports value width <= 256");
+  auto out = torch::zeros({n, (int64_t)vw}, X.options());
+  if (n > 0 && T > 0) {
+    const int cache_row = d <= FW_DMAX ? 1 : 0;
+    const size_t lds = cache_row ? (size_t)4 * d * sizeof(float) : 0;
+    TORCH_CHECK(lds <= 160 * 1024, "fil_predict_wide: row cache too large for LDS");
+    const unsigned grid = (unsigned)std::min<int64_t>(16384, (n + 3) / 4);
+    hipLaunchKernelGGL(fil_predict_wide_kernel, dim3(grid), dim3(256), lds, cur_stream(),
+                       X.data_ptr<float>(), feat.data_ptr<int32_t>(),
+                       thr.data_ptr<float>(), left.data_ptr<int32_t>(),
+                       right.data_ptr<int32_t>(), value.data_ptr<float>(),
+                       roots.data_ptr<int64_t>(), n, d, T, vw, cache_row,
+                       out.data_ptr<float>());
+    C10_HIP_KERNEL_LAUNCH_CHECK();
+  }
+  return out;
+}
+
 torch::Tensor csr_fwd(torch::Tensor indptr, torch::Tensor indices, torch::Tensor vals,
                       torch::Tensor WT) {
   TORCH_CHECK(vals.is_cuda() && vals.dtype() == torch::kFloat32);
@@ -6666,6 +7014,8 @@ torch::Tensor csr_col_moments(torch::Tensor indices, torch::Tensor vals, int64_t
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fil_predict", &fil_predict, "forest inference (FIL-style traversal)");
+  m.def("fil_predict_wide", &fil_predict_wide,
+        "classification forest inference, lanes over trees then classes (width <= 256)");
   m.def("csr_fwd", &csr_fwd, "CSR scores = A @ WT (thread per row)");
   m.def("csr_grad", &csr_grad, "CSR grad = (A^T R)^T by column scatter");
   m.def("csr_col_moments", &csr_col_moments, "per-column sum/sumsq of CSR values");
@@ -6699,6 +7049,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rf_histogram", &rf_histogram, "LDS-privatized RF split histograms");
   m.def("rf_histogram_fw", &rf_histogram_fw, "feature-wide RF histograms (lanes over sorted features)");
   m.def("rf_best_split", &rf_best_split, "fused RF gain scan + block-best reduce");
+  m.def("rf_best_split_scan", &rf_best_split_scan,
+        "RF gain scan, lanes over bins: gini/entropy, any class count");
   m.def("dbscan_sweep", &dbscan_sweep, "fused eps-neighborhood count / min-core-label pass");
   m.def("umap_sgd", &umap_sgd, "edge-sampled UMAP SGD (all epochs, Hogwild)");
   m.def("rf_partition", &rf_partition, "counting-sort rows by node -> (perm, seg_off)");

@@ -124,6 +124,24 @@ class _RandomForestParams(HasFeaturesCol, HasFeaturesCols, HasLabelCol, HasPredi
         return self.getOrDefault("maxDepth")
 
 
+_IMPURITIES = {"classification": ("gini", "entropy"), "regression": ("variance",)}
+
+
+def _resolve_impurity(value: Optional[str], task: str) -> str:
+    """The split criterion of a fit: the task's first impurity when unset;
+    anything the task does not accept is an error, as in Spark."""
+    accepted = _IMPURITIES[task]
+    if value is None:
+        return accepted[0]
+    crit = str(value).lower()
+    if crit not in accepted:
+        raise ValueError(
+            f"impurity={value!r} is not supported for {task}: accepted values are "
+            + ", ".join(repr(a) for a in accepted)
+        )
+    return crit
+
+
 def _estimators_per_worker(n_estimators: int, world: int) -> List[int]:
     """Tree counts per rank (reference tree.py:330-341): floor division with
     the remainder spread over the first ranks."""
@@ -337,6 +355,7 @@ def _grow_forest(
     sample: Optional[torch.Tensor] = None,  # int32 [n_trees*per] bootstrap map
     node_batch: int = 16384,
     feat_chunk: int = 256,
+    criterion: str = "gini",  # classification impurity: gini | entropy
 ) -> List[Dict[str, np.ndarray]]:
     """Grow ALL of this worker's trees at once in one node arena over a
     VIRTUAL row space [n_trees × per] (cuML-style batched node processing —
@@ -380,7 +399,7 @@ def _grow_forest(
     edges_np = as_numpy(edges)
     # virtual row v starts at its tree's root (arena ids 0..n_trees-1)
     node_of_row = t_of_v.clone()
-    levels = forest_backend(Xb, y, task, n_classes, n_bins, sample, feat_chunk)
+    levels = forest_backend(Xb, y, task, n_classes, n_bins, sample, feat_chunk, criterion)
     timer = RFTimer(dev)
     timer.debug(f"{levels.label} n={n} d={d} device={dev}")
     frontier = list(range(n_trees))  # arena node ids still splittable
@@ -542,6 +561,7 @@ class _RandomForestEstimator(_RandomForestParams, Estimator):
         seed = int(params["random_state"])
         bootstrap = bool(params["bootstrap"])
         max_samples = float(params["max_samples"])
+        criterion = _resolve_impurity(params.get("split_criterion"), self._task)
 
         timer = RFTimer(ctx.device)
         Xt = ctx.device_tensor(np.asarray(X, dtype=np.float32))
@@ -624,6 +644,7 @@ class _RandomForestEstimator(_RandomForestParams, Estimator):
                         n_trees=g_trees,
                         sample=sample,
                         node_batch=int(params["max_batch_size"]),
+                        criterion=criterion,
                     )
                 )
                 t0g += g_trees

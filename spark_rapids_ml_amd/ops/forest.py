@@ -5,16 +5,17 @@ rerouted, behind one small surface with two backends.
 
 - HIP (gfx950): `rf_partition` (counting sort of rows by node) ->
   `rf_histogram` / `rf_histogram_fw` (LDS-privatized per-(node, feature
-  chunk) histograms) -> `rf_best_split` (fused gain scan + argmax) ->
-  `rf_reroute`.
+  chunk) histograms) -> `rf_best_split` (fused gain scan + argmax; Gini up
+  to 16 classes, regression) or `rf_best_split_scan` (entropy, and Gini past
+  16 classes) -> `rf_reroute`.
 - torch (CPU): `nonzero` / gather -> `index_add_` histograms ->
   `_best_split_class` / `_best_split_reg` -> gather reroute.
 
 Both expose `partition(node_of_row, lut, B)`, `best_splits(feat_sel, mf, B,
 min_leaf)` and `reroute(node_of_row, lut2, f, b, l, r)`; the grower in
 `models/tree.py` drives them without knowing which one it holds. Forest
-inference (`forest_predict`: `fil_predict` kernel or the level-wise torch
-traversal) and the `SRML_RF_DEBUG` timer live here too.
+inference (`forest_predict`: `fil_predict` / `fil_predict_wide` kernels or the
+level-wise torch traversal) and the `SRML_RF_DEBUG` timer live here too.
 """
 
 from __future__ import annotations
@@ -90,10 +91,13 @@ def _max_lastdim(t: torch.Tensor):
     return torch.from_numpy(np.ascontiguousarray(vals)), torch.from_numpy(idx.astype(np.int64))
 
 
-def _best_split_class(H: torch.Tensor, min_leaf: int):
+CRITERIA = ("gini", "entropy")  # classification; index = kernel criterion code
+
+
+def _best_split_class(H: torch.Tensor, min_leaf: int, criterion: str = "gini"):
     """H: [B,F,nb,C] class counts. Returns per (B,F): best gain (impurity
-    decrease weighted by node fraction, Spark/CART gini), split bin, left/right
-    class-count values, left count."""
+    decrease weighted by node fraction, Spark/CART gini or entropy in bits),
+    split bin, left/right class-count values, left count."""
     csum = H.cumsum(dim=2)  # left counts for split at bin b (bins <= b)
     total = csum[:, :, -1:, :]  # [B,F,1,C]
     left = csum[:, :, :-1, :]  # split bins 0..nb-2
@@ -101,12 +105,18 @@ def _best_split_class(H: torch.Tensor, min_leaf: int):
     lc = left.sum(dim=3)
     rc = right.sum(dim=3)
     nt = total.sum(dim=3)  # [B,F,1]
-    gini = lambda cnt, tot: 1.0 - ((cnt / torch.clamp(tot.unsqueeze(-1), min=1e-12)) ** 2).sum(
-        dim=-1
-    )
-    g_parent = gini(total, nt)  # [B,F,1]
-    g_left = gini(left, lc)
-    g_right = gini(right, rc)
+    if criterion == "entropy":
+        # -sum p log2 p (Spark Entropy.calculate), p log2 p = 0 at p = 0
+        def imp(cnt, tot):
+            p = cnt / torch.clamp(tot.unsqueeze(-1), min=1e-12)
+            return -torch.xlogy(p, p).sum(dim=-1) / float(np.log(2.0))
+    else:
+        imp = lambda cnt, tot: 1.0 - (
+            (cnt / torch.clamp(tot.unsqueeze(-1), min=1e-12)) ** 2
+        ).sum(dim=-1)
+    g_parent = imp(total, nt)  # [B,F,1]
+    g_left = imp(left, lc)
+    g_right = imp(right, rc)
     ntc = torch.clamp(nt, min=1e-12)
     gain = g_parent - (lc / ntc) * g_left - (rc / ntc) * g_right  # [B,F,nb-1]
     valid = (lc >= min_leaf) & (rc >= min_leaf)
@@ -151,11 +161,14 @@ def _best_split_reg(H: torch.Tensor, min_leaf: int):
     return best_gain, best_bin, lval, rval, lcb
 
 
-def _scan_chunk(H: torch.Tensor, classification: bool, min_leaf: int):
-    """Torch twin of the rf_best_split kernel: per node the best (gain,
-    column within the chunk, bin, left value, right value) of H [B,F,nb,C]."""
-    scan = _best_split_class if classification else _best_split_reg
-    gain, sbin, lval, rval, _ = scan(H, min_leaf)
+def _scan_chunk(H: torch.Tensor, classification: bool, min_leaf: int, criterion: str = "gini"):
+    """Torch twin of the rf_best_split / rf_best_split_scan kernels: per node
+    the best (gain, column within the chunk, bin, left value, right value) of
+    H [B,F,nb,C]."""
+    if classification:
+        gain, sbin, lval, rval, _ = _best_split_class(H, min_leaf, criterion)
+    else:
+        gain, sbin, lval, rval, _ = _best_split_reg(H, min_leaf)
     g, col = _max_lastdim(gain)
     ar = torch.arange(H.shape[0], device=H.device)
     return g, col, sbin[ar, col], lval[ar, col], rval[ar, col]
@@ -196,8 +209,9 @@ class _TorchLevels:
 
     label = "hip_hist=False"
 
-    def __init__(self, Xb, y, task, n_classes, n_bins, sample, feat_chunk):
+    def __init__(self, Xb, y, task, n_classes, n_bins, sample, feat_chunk, criterion="gini"):
         self.Xb, self.n_bins, self.feat_chunk = Xb, n_bins, feat_chunk
+        self.criterion = criterion
         self.classification = task == "classification"
         self.width = n_classes if self.classification else 2
         self.y = y.to(torch.int64) if self.classification else y.to(torch.float32)
@@ -245,7 +259,7 @@ class _TorchLevels:
             else:
                 bins = self.Xb[self.prows[:, None], src[:, f0:f1]].to(torch.int64)
             g, col, sbin, lval, rval = _scan_chunk(
-                self._histogram(bins, B), self.classification, min_leaf
+                self._histogram(bins, B), self.classification, min_leaf, self.criterion
             )
             feat = col + f0 if feat_sel is None else feat_sel[ar, col + f0]
             best.merge(g, feat, sbin, lval, rval)
@@ -265,9 +279,13 @@ class _HipLevels:
 
     label = "hip_hist=True"
 
-    def __init__(self, ext, Xb, y, task, n_classes, n_bins, sample):
+    def __init__(self, ext, Xb, y, task, n_classes, n_bins, sample, criterion="gini"):
         self.ext, self.Xb, self.n_bins = ext, Xb, n_bins
         self.classification = task == "classification"
+        self.criterion = criterion
+        # SRML_RF_SCAN=torch: the torch scan over the kernel histogram where
+        # rf_best_split_scan would run (A/B runs only)
+        self.torch_scan = os.environ.get("SRML_RF_SCAN") == "torch"
         self.n_classes = n_classes if self.classification else 0
         self.width = n_classes if self.classification else 2
         self.y32 = y.to(torch.int32) if self.classification else y.to(torch.float32)
@@ -328,11 +346,21 @@ class _HipLevels:
                 hist_x, self.perm, self.seg_off, fsel32, self.y32, f0, F,
                 self.n_bins, self.n_classes, self.sample, self.y_max,
             )
-            if H.shape[3] <= 16:
-                # fused gain scan + per-node best (kernel)
-                g, col, sbin, lval, rval = self.ext.rf_best_split(
-                    H, min_leaf, self.classification
-                )
+            narrow = not self.classification or (
+                self.criterion == "gini" and H.shape[3] <= 16
+            )
+            if narrow or not self.torch_scan:
+                # fused gain scan + per-node best: threads over features with
+                # the classes in registers (Gini up to 16 classes, regression),
+                # else lanes over bins with the classes streamed
+                if narrow:
+                    g, col, sbin, lval, rval = self.ext.rf_best_split(
+                        H, min_leaf, self.classification
+                    )
+                else:
+                    g, col, sbin, lval, rval = self.ext.rf_best_split_scan(
+                        H, min_leaf, CRITERIA.index(self.criterion)
+                    )
                 col = col.to(torch.int64) + f0
                 # a node without a valid split reports column -1
                 feat = col if feat_sel is None else feat_sel[ar, col.clamp(min=0)]
@@ -340,9 +368,9 @@ class _HipLevels:
                 if not self.classification:
                     lval, rval = self._mean_count(lval), self._mean_count(rval)
             else:
-                # rf_best_split scans at most 16 channels: torch scan over
-                # the kernel histogram past that
-                g, col, sbin, lval, rval = _scan_chunk(H, self.classification, min_leaf)
+                g, col, sbin, lval, rval = _scan_chunk(
+                    H, self.classification, min_leaf, self.criterion
+                )
                 feat = col + f0 if feat_sel is None else feat_sel[ar, col + f0]
             best.merge(g, feat, sbin, lval, rval)
         return best.result()
@@ -368,11 +396,14 @@ def forest_backend(
     n_bins: int,
     sample: Optional[torch.Tensor] = None,  # int32 virtual -> physical row map
     feat_chunk: int = 256,  # torch backend's features per histogram
+    criterion: str = "gini",  # classification impurity: gini | entropy
 ):
     """The level backend for this forest, chosen once from the device."""
+    if task == "classification" and criterion not in CRITERIA:
+        raise ValueError(f"criterion must be one of {CRITERIA}, got {criterion!r}")
     if use_hip(Xb):
-        return _HipLevels(hip_ops(), Xb, y, task, n_classes, n_bins, sample)
-    return _TorchLevels(Xb, y, task, n_classes, n_bins, sample, feat_chunk)
+        return _HipLevels(hip_ops(), Xb, y, task, n_classes, n_bins, sample, criterion)
+    return _TorchLevels(Xb, y, task, n_classes, n_bins, sample, feat_chunk, criterion)
 
 
 # ---------------------------------------------------------------------------
@@ -418,6 +449,9 @@ def forest_traverse(
     return acc
 
 
+FIL_WIDE_MAX = 256  # fil_predict_wide: 4 vote registers per lane x 64 lanes
+
+
 def forest_predict(
     Xt: torch.Tensor,  # [n,d] f32
     trees: List[Dict[str, np.ndarray]],
@@ -429,13 +463,20 @@ def forest_predict(
     fil_predict kernel — one thread walks every tree for its row over the
     flattened node arena `arena(device)` builds (the reference's FIL predict,
     tree.py:709-721); its per-thread vote registers hold up to 16 values.
+    Classification past that, up to FIL_WIDE_MAX classes: fil_predict_wide
+    (one wave per row, lanes over trees, then lanes over classes).
     Otherwise the torch traversal."""
     width = n_classes if task == "classification" else 2
-    if use_hip(Xt) and 0 < width <= 16 and Xt.shape[0] > 0 and len(trees) > 0:
+    if use_hip(Xt) and 0 < width <= FIL_WIDE_MAX and Xt.shape[0] > 0 and len(trees) > 0:
         a = arena(Xt.device)
-        out = hip_ops().fil_predict(
+        if width <= 16:
+            out = hip_ops().fil_predict(
+                Xt.contiguous(), a["feat"], a["thr"], a["left"], a["right"],
+                a["value"], a["roots"], task == "classification",
+            )
+            return out if task == "classification" else out[:, 0]
+        return hip_ops().fil_predict_wide(
             Xt.contiguous(), a["feat"], a["thr"], a["left"], a["right"],
-            a["value"], a["roots"], task == "classification",
+            a["value"], a["roots"],
         )
-        return out if task == "classification" else out[:, 0]
     return forest_traverse(Xt, trees, task, n_classes)

@@ -464,10 +464,11 @@ def _save_logreg(model, path: str) -> None:
 
 
 def _tree_to_nodedata(
-    t: Dict[str, np.ndarray], classification: bool
+    t: Dict[str, np.ndarray], classification: bool, impurity: str = "gini"
 ) -> List[Tuple[int, float, float, List[float], int, float, int, int, int, List[float], int]]:
     """Convert one of our flat trees to Spark NodeData rows with PRE-ORDER
-    ids (Spark DecisionTreeModelReadWrite.NodeData.build numbering).
+    ids (Spark DecisionTreeModelReadWrite.NodeData.build numbering). A
+    classification node's impurity is the model's: gini, or entropy in bits.
 
     Returns tuples: (id, prediction, impurity, impurityStats, rawCount,
     gain, leftChild, rightChild, splitFeature, splitThresholds, numCategories)
@@ -488,8 +489,12 @@ def _tree_to_nodedata(
             cnt = float(v.sum())
             pred = float(np.argmax(v))
             p = v / max(cnt, 1e-300)
-            impurity = float(1.0 - (p * p).sum())  # gini
-            return pred, impurity, v.tolist(), int(round(cnt))
+            if impurity == "entropy":
+                nz = p[p > 0]
+                imp = float(-(nz * np.log2(nz)).sum())
+            else:
+                imp = float(1.0 - (p * p).sum())
+            return pred, imp, v.tolist(), int(round(cnt))
         mean, cnt = float(v[0]), float(v[1])
         # sum-of-squares not retained post-fit: stats reproduce the mean and
         # count exactly, node impurity reads as 0 (documented deviation)
@@ -604,6 +609,7 @@ def _save_random_forest(model, path: str, classification: bool) -> None:
         "minInstancesPerNode", "minInfoGain",
     )}
     trees = model.trees
+    impurity = str({**dm, **pm}.get("impurity", "gini")).lower()
     tm_rows = []
     for i in range(len(trees)):
         tj = {
@@ -633,7 +639,7 @@ def _save_random_forest(model, path: str, classification: bool) -> None:
     for tid, t in enumerate(trees):
         for (
             nid, pred, imp, stats, raw, g, lc, rc, sf, sthr, ncat
-        ) in _tree_to_nodedata(t, classification):
+        ) in _tree_to_nodedata(t, classification, impurity):
             tree_ids.append(tid)
             node_rows.append(
                 {

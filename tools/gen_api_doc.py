@@ -103,6 +103,18 @@ search could not fill report id `-1` and `+inf`.
 
 Any other DBSCAN metric raises `ValueError` at `transform`.
 
+`RandomForestClassifier(impurity=...)` accepts `gini` and `entropy` (in bits, \
+as Spark's `Entropy`), `RandomForestRegressor` accepts `variance`; anything \
+else raises `ValueError` naming the accepted values at `fit`. Trees are grown \
+on the chosen criterion, the stored node gains are in it, and \
+`saveAsSparkModel` writes node impurities in it. On the GPU, Gini up to 16 \
+classes and regression scan splits with `rf_best_split`; entropy, and Gini \
+past 16 classes, with `rf_best_split_scan` (any class count, `maxBins <= 256`; \
+`SRML_RF_SCAN=torch` forces the torch scan for A/B runs). `transform` of a \
+classifier with 17 to 256 classes runs `fil_predict_wide`; past 256 classes \
+the torch traversal. The histogram kernels keep their own limit: one \
+feature's `maxBins * numClasses` cells must fit 160 KB of LDS.
+
 `UMAP(metric=..., metric_kwds={"p": ...})` (reference umap.py metric list). Only the kNN stage of fit and transform depends on the metric; a fitted model keeps its estimator's `metric` / `metric_kwds` (also through save / load) and transforms with them. All errors are `ValueError`.
 
 | metric (aliases) | distance | kNN path on the GPU | `build_algo="nn_descent"` |
