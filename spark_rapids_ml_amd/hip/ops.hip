@@ -905,18 +905,26 @@ __global__ __launch_bounds__(256) void segment_reduce_f64_kernel(
 // Per column the rows are added in segment_sum's order and grouping, so sums
 // and counts equal label_accumulate's. VEC (d % 4 == 0, 16-byte aligned
 // bases): each lane loads float4s, 4 per row instead of 16 scalars.
+//
+// ANCHOR (the full pass of the delta step, see kmeans_delta_accumulate): the
+// block adds its squares into inertia[lab], so the caller gets the per-label
+// second moments Q about the anchors c, and a second accumulator set sums
+// (x - c) into `dsums`: the first moment about the same anchors, free of the
+// f32 rounding that sum x carries for data far from the origin (sum x itself
+// is still returned, bit for bit as without the flag).
 // ---------------------------------------------------------------------------
 
 constexpr bool LA_VEC_DEFAULT = true;
 
-template <bool VEC>
+template <bool VEC, bool ANCHOR>
 __global__ __launch_bounds__(256) void segment_sum_inertia_kernel(
     const float* __restrict__ X, const int64_t* __restrict__ perm,
     const int64_t* __restrict__ seg_off, const float* __restrict__ C, int d,
     float* __restrict__ sums, float* __restrict__ counts,
-    double* __restrict__ inertia) {
+    double* __restrict__ inertia, float* __restrict__ dsums) {
   constexpr int W = VEC ? 4 : 1;      // columns per load
   constexpr int NQ = LA_COLS / W;     // loads per thread and row
+  constexpr int NA = ANCHOR ? LA_COLS : 1;
   const int lab = blockIdx.x / LA_SPLIT;
   const int split = blockIdx.x % LA_SPLIT;
   const int64_t s0 = seg_off[lab], e0 = seg_off[lab + 1];
@@ -940,7 +948,9 @@ __global__ __launch_bounds__(256) void segment_sum_inertia_kernel(
   const float* crow = C + (int64_t)lab * d;
   double local = 0.0;
   for (int cb = 0; cb < d; cb += blockDim.x * LA_COLS) {
-    float acc[LA_COLS], cen[LA_COLS];
+    float acc[LA_COLS], cen[LA_COLS], dac[NA];
+#pragma unroll
+    for (int q = 0; q < NA; ++q) dac[q] = 0.0f;
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
       const int c = cb + (q * blockDim.x + threadIdx.x) * W;
@@ -964,8 +974,9 @@ __global__ __launch_bounds__(256) void segment_sum_inertia_kernel(
 #pragma unroll
           for (int w = 0; w < W; ++w) {
             const float ce = cen[q * W + w];
-            acc[q * W + w] += x0[w] + x1[w] + x2[w] + x3[w];
             const float f0 = x0[w] - ce, f1 = x1[w] - ce, f2 = x2[w] - ce, f3 = x3[w] - ce;
+            acc[q * W + w] += x0[w] + x1[w] + x2[w] + x3[w];
+            if constexpr (ANCHOR) dac[q * W + w] += f0 + f1 + f2 + f3;
             part = fmaf(f0, f0, part); part = fmaf(f1, f1, part);
             part = fmaf(f2, f2, part); part = fmaf(f3, f3, part);
           }
@@ -984,8 +995,9 @@ __global__ __launch_bounds__(256) void segment_sum_inertia_kernel(
           ld(row + c, x0);
 #pragma unroll
           for (int w = 0; w < W; ++w) {
-            acc[q * W + w] += x0[w];
             const float f0 = x0[w] - cen[q * W + w];
+            acc[q * W + w] += x0[w];
+            if constexpr (ANCHOR) dac[q * W + w] += f0;
             part = fmaf(f0, f0, part);
           }
         }
@@ -1002,6 +1014,7 @@ __global__ __launch_bounds__(256) void segment_sum_inertia_kernel(
             atomicAdd(&sums[(int64_t)lab * d + c + w], acc[q * W + w]);
           else
             sums[(int64_t)lab * d + c + w] = acc[q * W + w];
+          if constexpr (ANCHOR) atomicAdd(&dsums[(int64_t)lab * d + c + w], dac[q * W + w]);
         }
       }
     }
@@ -1013,7 +1026,255 @@ __global__ __launch_bounds__(256) void segment_sum_inertia_kernel(
     if (threadIdx.x < off) red_s[threadIdx.x] += red_s[threadIdx.x + off];
     __syncthreads();
   }
-  if (threadIdx.x == 0) atomicAdd(inertia, red_s[0]);
+  if (threadIdx.x == 0) atomicAdd(ANCHOR ? inertia + lab : inertia, red_s[0]);
+}
+
+// ---------------------------------------------------------------------------
+// The delta step: between two Lloyd steps only the rows that changed label
+// move the per-centre moments, so they are kept from step to step about a
+// fixed anchor r_j per centre (the centre at the last full pass),
+//   n_j,  S_j = sum_{i in j} (x_i - r_j),  Q_j = sum_{i in j} |x_i - r_j|^2,
+// and a step updates them from the changed rows alone. Then
+//   sum_{i in j} x_i           = S_j + n_j r_j
+//   sum_{i in j} |x_i - c_j|^2 = Q_j - 2 (c_j - r_j).S_j + n_j |c_j - r_j|^2,
+// the last two terms small corrections while c_j stays near r_j.
+//
+// kmeans_label_delta: one thread per row; a row with labels[i] != prev[i]
+// appends two signed entries (one ballot and one atomic per wave, as the
+// screen does): (prev[i], ~i) takes the row out of its old label, (labels[i],
+// i) puts it into the new one. prev[i] = labels[i] afterwards.
+// ---------------------------------------------------------------------------
+
+__global__ __launch_bounds__(256) void kmeans_label_delta_kernel(
+    const int32_t* __restrict__ labels, int32_t* __restrict__ prev, int64_t n,
+    int32_t* __restrict__ ent_lab,    // [2n]
+    int32_t* __restrict__ ent_row,    // [2n] row, or ~row for a removal
+    int32_t* __restrict__ n_changed) {  // [1] accumulated
+  const int lane = threadIdx.x & 63;
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  // i0 is block-uniform so every lane reaches the ballot below
+  for (int64_t i0 = (int64_t)blockIdx.x * 256; i0 < n; i0 += stride) {
+    const int64_t i = i0 + threadIdx.x;
+    const bool valid = i < n;
+    const int32_t ln = valid ? labels[i] : 0;
+    const int32_t lo = valid ? prev[i] : 0;
+    const bool flag = valid && ln != lo;
+    const unsigned long long mask = __ballot(flag);
+    if (mask != 0ull) {
+      const int leader = __ffsll((long long)mask) - 1;
+      int base = 0;
+      if (lane == leader) base = atomicAdd(n_changed, __popcll(mask));
+      base = __shfl(base, leader, 64);
+      if (flag) {
+        const int64_t p = 2 * ((int64_t)base + __popcll(mask & ((1ull << lane) - 1ull)));
+        ent_lab[p] = lo;
+        ent_row[p] = ~(int32_t)i;
+        ent_lab[p + 1] = ln;
+        ent_row[p + 1] = (int32_t)i;
+        prev[i] = ln;
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// kmeans_delta_accumulate, sorted form: the 2m signed entries sorted by label
+// (torch.sort in the wrapper), each (label, split) block streams its
+// sub-segment with segment_sum's column layout and adds sign * (x - r) and
+// sign * (x - r)^2 in f64 per thread (mixed signs stay exact on integers).
+// One f64 atomic per column into S, one into Q[lab] and one into cnt[lab] per
+// block. `nsplit` (1..LA_SPLIT, from the wrapper) follows the entry count:
+// a handful of entries per label is one block's work.
+// ---------------------------------------------------------------------------
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void delta_segment_kernel(
+    const float* __restrict__ X, const int32_t* __restrict__ ent_row,
+    const int64_t* __restrict__ perm, const int64_t* __restrict__ seg_off,
+    const float* __restrict__ R, int d, int nsplit,
+    double* __restrict__ S, double* __restrict__ cnt, double* __restrict__ Q) {
+  constexpr int W = VEC ? 4 : 1;
+  constexpr int NQ = LA_COLS / W;
+  const int lab = blockIdx.x / nsplit;
+  const int split = blockIdx.x % nsplit;
+  const int64_t s0 = seg_off[lab], e0 = seg_off[lab + 1];
+  const int64_t len = e0 - s0;
+  if (len == 0) return;
+  const int64_t chunk = (len + nsplit - 1) / nsplit;
+  const int64_t rs = s0 + split * chunk;
+  const int64_t re = min(e0, rs + chunk);
+  if (rs >= re) return;  // block-uniform: no barrier is skipped by part of a block
+
+  auto ld = [](const float* p, float* out) {
+    if constexpr (VEC) {
+      const float4 v = *reinterpret_cast<const float4*>(p);
+      out[0] = v.x; out[1] = v.y; out[2] = v.z; out[3] = v.w;
+    } else {
+      out[0] = *p;
+    }
+  };
+
+  const float* rrow = R + (int64_t)lab * d;
+  double local = 0.0;
+  int net = 0;
+  for (int cb = 0; cb < d; cb += blockDim.x * LA_COLS) {
+    double acc[LA_COLS];
+    float anc[LA_COLS];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      const int c = cb + (q * blockDim.x + threadIdx.x) * W;
+#pragma unroll
+      for (int w = 0; w < W; ++w) { acc[q * W + w] = 0.0; anc[q * W + w] = 0.0f; }
+      if (c < d) ld(rrow + c, anc + q * W);  // VEC: d % 4 == 0, all 4 inside
+    }
+    int64_t r = rs;
+    for (; r + 2 <= re; r += 2) {  // 2 rows in flight
+      const int32_t e0r = ent_row[perm[r]], e1r = ent_row[perm[r + 1]];
+      const double sg0 = e0r < 0 ? -1.0 : 1.0, sg1 = e1r < 0 ? -1.0 : 1.0;
+      const float* row0 = X + (int64_t)(e0r < 0 ? ~e0r : e0r) * d;
+      const float* row1 = X + (int64_t)(e1r < 0 ? ~e1r : e1r) * d;
+      if (cb == 0) net += (e0r < 0 ? -1 : 1) + (e1r < 0 ? -1 : 1);
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) {
+        const int c = cb + (q * blockDim.x + threadIdx.x) * W;
+        if (c < d) {
+          float x0[W], x1[W];
+          ld(row0 + c, x0); ld(row1 + c, x1);
+#pragma unroll
+          for (int w = 0; w < W; ++w) {
+            const double a = (double)anc[q * W + w];
+            const double f0 = (double)x0[w] - a, f1 = (double)x1[w] - a;
+            acc[q * W + w] += sg0 * f0 + sg1 * f1;
+            local += sg0 * (f0 * f0) + sg1 * (f1 * f1);
+          }
+        }
+      }
+    }
+    for (; r < re; ++r) {
+      const int32_t e0r = ent_row[perm[r]];
+      const double sg0 = e0r < 0 ? -1.0 : 1.0;
+      const float* row0 = X + (int64_t)(e0r < 0 ? ~e0r : e0r) * d;
+      if (cb == 0) net += e0r < 0 ? -1 : 1;
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) {
+        const int c = cb + (q * blockDim.x + threadIdx.x) * W;
+        if (c < d) {
+          float x0[W];
+          ld(row0 + c, x0);
+#pragma unroll
+          for (int w = 0; w < W; ++w) {
+            const double f0 = (double)x0[w] - (double)anc[q * W + w];
+            acc[q * W + w] += sg0 * f0;
+            local += sg0 * (f0 * f0);
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      const int c = cb + (q * blockDim.x + threadIdx.x) * W;
+      if (c < d) {
+#pragma unroll
+        for (int w = 0; w < W; ++w)
+          if (acc[q * W + w] != 0.0) atomicAdd(&S[(int64_t)lab * d + c + w], acc[q * W + w]);
+      }
+    }
+  }
+  __shared__ double red_s[256];
+  red_s[threadIdx.x] = local;
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) {
+    if (threadIdx.x < off) red_s[threadIdx.x] += red_s[threadIdx.x + off];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    atomicAdd(&Q[lab], red_s[0]);
+    if (net != 0) atomicAdd(&cnt[lab], (double)net);
+  }
+}
+
+// ---------------------------------------------------------------------------
+// kmeans_delta_accumulate, direct form: no sort. One block per entry, grid-
+// stride over the device-side count as kmeans_refine does, every column an
+// f64 atomic into S. Kept beside the sorted form for the comparison in
+// profiles/README.md ("Delta step").
+// ---------------------------------------------------------------------------
+
+__global__ __launch_bounds__(256) void delta_direct_kernel(
+    const float* __restrict__ X, const int32_t* __restrict__ ent_lab,
+    const int32_t* __restrict__ ent_row, const int32_t* __restrict__ n_changed,
+    int64_t max_entries, const float* __restrict__ R, int d, int k,
+    double* __restrict__ S, double* __restrict__ cnt, double* __restrict__ Q) {
+  __shared__ double red_s[256];
+  const int64_t ne = min(2 * (int64_t)n_changed[0], max_entries);
+  for (int64_t e = blockIdx.x; e < ne; e += gridDim.x) {  // block-uniform
+    const int lab = ent_lab[e];
+    if (lab < 0 || lab >= k) continue;
+    const int32_t er = ent_row[e];
+    const double sg = er < 0 ? -1.0 : 1.0;
+    const float* row = X + (int64_t)(er < 0 ? ~er : er) * d;
+    const float* rrow = R + (int64_t)lab * d;
+    double local = 0.0;
+    for (int c = threadIdx.x; c < d; c += 256) {
+      const double f = (double)row[c] - (double)rrow[c];
+      if (f != 0.0) atomicAdd(&S[(int64_t)lab * d + c], sg * f);
+      local += f * f;
+    }
+    red_s[threadIdx.x] = local;
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+      if (threadIdx.x < off) red_s[threadIdx.x] += red_s[threadIdx.x + off];
+      __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+      atomicAdd(&Q[lab], sg * red_s[0]);
+      atomicAdd(&cnt[lab], sg);
+    }
+    __syncthreads();  // red_s is reused by the next entry
+  }
+}
+
+// ---------------------------------------------------------------------------
+// kmeans_anchor_inertia: one block per centre, all in f64. Writes the centre's
+// row of sums, S_j + n_j r_j + E_j (E: what the caller's f32 sum x of the last
+// full pass differed by, so that the sums continue from those), and adds into
+// out[0] the inertia term max(0, Q_j - 2 (c_j - r_j).S_j + n_j |c_j - r_j|^2),
+// into out[1] the drift n_j |c_j - r_j|^2 and into out[2] Q_j.
+// ---------------------------------------------------------------------------
+
+__global__ __launch_bounds__(256) void kmeans_anchor_inertia_kernel(
+    const float* __restrict__ C, const float* __restrict__ R,
+    const double* __restrict__ S, const double* __restrict__ cnt,
+    const double* __restrict__ Q, const double* __restrict__ E, int d,
+    double* __restrict__ sums, double* __restrict__ out) {  // out: [3] accumulated
+  const int j = blockIdx.x;
+  const double nj = cnt[j];
+  double dot = 0.0, sq = 0.0;
+  for (int c = threadIdx.x; c < d; c += 256) {
+    const int64_t o = (int64_t)j * d + c;
+    const double r = (double)R[o], s = S[o];
+    const double df = (double)C[o] - r;
+    dot = fma(df, s, dot);
+    sq = fma(df, df, sq);
+    sums[o] = s + nj * r + E[o];
+  }
+  __shared__ double red_a[256], red_b[256];
+  red_a[threadIdx.x] = dot;
+  red_b[threadIdx.x] = sq;
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) {
+    if (threadIdx.x < off) {
+      red_a[threadIdx.x] += red_a[threadIdx.x + off];
+      red_b[threadIdx.x] += red_b[threadIdx.x + off];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const double drift = nj * red_b[0];
+    atomicAdd(&out[0], fmax(0.0, Q[j] - 2.0 * red_a[0] + drift));
+    atomicAdd(&out[1], drift);
+    atomicAdd(&out[2], Q[j]);
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -5605,9 +5866,11 @@ std::vector<torch::Tensor> label_accumulate(torch::Tensor X, torch::Tensor label
 
 // (sums [k,d], counts [k], inertia f64 [1]) on the sorted segment path, k and
 // the centres taken from C. `vec` selects the 16-byte row loads where the
-// layout allows them.
+// layout allows them. `anchor` asks for the moments about C instead, the full
+// pass of the delta step: two more tensors, Q f64 [k], the per-label sum
+// |x - c|^2 (the inertia is its sum), and sum (x - c) f32 [k,d].
 std::vector<torch::Tensor> label_accumulate_inertia(torch::Tensor X, torch::Tensor labels,
-                                                    torch::Tensor C, bool vec) {
+                                                    torch::Tensor C, bool vec, bool anchor) {
   TORCH_CHECK(X.is_cuda() && labels.is_cuda() && C.is_cuda(), "device tensors required");
   TORCH_CHECK(X.dtype() == torch::kFloat32 && X.is_contiguous() && X.dim() == 2);
   TORCH_CHECK(C.dtype() == torch::kFloat32 && C.is_contiguous() && C.dim() == 2);
@@ -5618,28 +5881,147 @@ std::vector<torch::Tensor> label_accumulate_inertia(torch::Tensor X, torch::Tens
   const int d = (int)X.size(1);
   auto sums = torch::zeros({k, d}, X.options());
   auto counts = torch::zeros({k}, X.options());
-  auto inertia = torch::zeros({1}, X.options().dtype(torch::kFloat64));
-  if (n == 0 || k == 0) return {sums, counts, inertia};
+  auto inertia = torch::zeros({anchor ? std::max<int64_t>(k, 1) : 1},
+                              X.options().dtype(torch::kFloat64));
+  auto dsums = anchor ? torch::zeros({k, d}, X.options()) : torch::Tensor();
+  if (n == 0 || k == 0) {
+    if (anchor)
+      return {sums, counts, inertia.sum().reshape({1}), inertia.narrow(0, 0, k), dsums};
+    return {sums, counts, inertia};
+  }
   auto sorted = labels.to(torch::kInt64).sort();
   auto perm = std::get<1>(sorted).contiguous();
   auto sl = std::get<0>(sorted).contiguous();
   auto bounds = torch::arange(k + 1, labels.options().dtype(torch::kInt64));
   auto seg_off = torch::searchsorted(sl, bounds).contiguous();
   const bool aligned = ((uintptr_t)X.data_ptr() | (uintptr_t)C.data_ptr()) % 16 == 0;
-  if (vec && d % 4 == 0 && aligned)
-    hipLaunchKernelGGL(segment_sum_inertia_kernel<true>, dim3((unsigned)(k * LA_SPLIT)),
-                       dim3(256), 0, cur_stream(), X.data_ptr<float>(),
-                       perm.data_ptr<int64_t>(), seg_off.data_ptr<int64_t>(),
-                       C.data_ptr<float>(), d, sums.data_ptr<float>(),
-                       counts.data_ptr<float>(), inertia.data_ptr<double>());
-  else
-    hipLaunchKernelGGL(segment_sum_inertia_kernel<false>, dim3((unsigned)(k * LA_SPLIT)),
-                       dim3(256), 0, cur_stream(), X.data_ptr<float>(),
-                       perm.data_ptr<int64_t>(), seg_off.data_ptr<int64_t>(),
-                       C.data_ptr<float>(), d, sums.data_ptr<float>(),
-                       counts.data_ptr<float>(), inertia.data_ptr<double>());
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)(k * LA_SPLIT)), dim3(256), 0, cur_stream(),
+                       X.data_ptr<float>(), perm.data_ptr<int64_t>(),
+                       seg_off.data_ptr<int64_t>(), C.data_ptr<float>(), d,
+                       sums.data_ptr<float>(), counts.data_ptr<float>(),
+                       inertia.data_ptr<double>(),
+                       anchor ? dsums.data_ptr<float>() : nullptr);
+  };
+  const bool v = vec && d % 4 == 0 && aligned;
+  if (anchor) {
+    if (v) launch(segment_sum_inertia_kernel<true, true>);
+    else launch(segment_sum_inertia_kernel<false, true>);
+  } else {
+    if (v) launch(segment_sum_inertia_kernel<true, false>);
+    else launch(segment_sum_inertia_kernel<false, false>);
+  }
   C10_HIP_KERNEL_LAUNCH_CHECK();
+  if (anchor) return {sums, counts, inertia.sum().reshape({1}), inertia, dsums};
   return {sums, counts, inertia};
+}
+
+// (ent_lab i32 [2n], ent_row i32 [2n], n_changed i32 [1]): the signed entries
+// of the rows whose label differs from `prev`, which is brought up to date.
+std::vector<torch::Tensor> kmeans_label_delta(torch::Tensor labels, torch::Tensor prev) {
+  for (const torch::Tensor* t : {&labels, &prev})
+    TORCH_CHECK(t->is_cuda() && t->dtype() == torch::kInt32 && t->is_contiguous() &&
+                    t->dim() == 1,
+                "kmeans_label_delta takes contiguous int32 device vectors");
+  const int64_t n = labels.numel();
+  TORCH_CHECK(prev.numel() == n, "labels and prev sizes disagree");
+  TORCH_CHECK(n < ((int64_t)1 << 30), "too many rows for int32 entry ids");
+  auto ent_lab = torch::empty({2 * n}, labels.options());
+  auto ent_row = torch::empty({2 * n}, labels.options());
+  auto n_changed = torch::zeros({1}, labels.options());
+  if (n > 0) {
+    const unsigned grid = (unsigned)std::min<int64_t>(4096, (n + 255) / 256);
+    hipLaunchKernelGGL(kmeans_label_delta_kernel, dim3(grid), dim3(256), 0, cur_stream(),
+                       labels.data_ptr<int32_t>(), prev.data_ptr<int32_t>(), n,
+                       ent_lab.data_ptr<int32_t>(), ent_row.data_ptr<int32_t>(),
+                       n_changed.data_ptr<int32_t>());
+    C10_HIP_KERNEL_LAUNCH_CHECK();
+  }
+  return {ent_lab, ent_row, n_changed};
+}
+
+// Applies the entries of kmeans_label_delta to the moments about the anchors
+// R: S [k,d], cnt [k] and Q [k], f64 and in place. `m` is the changed count the host has read
+// from n_changed. `sorted` picks the form (see the kernels).
+void kmeans_delta_accumulate(torch::Tensor X, torch::Tensor ent_lab, torch::Tensor ent_row,
+                             torch::Tensor n_changed, int64_t m, torch::Tensor R,
+                             torch::Tensor S, torch::Tensor cnt, torch::Tensor Q,
+                             bool sorted) {
+  TORCH_CHECK(X.is_cuda() && X.dtype() == torch::kFloat32 && X.is_contiguous() && X.dim() == 2);
+  TORCH_CHECK(R.is_cuda() && R.dtype() == torch::kFloat32 && R.is_contiguous() && R.dim() == 2);
+  for (const torch::Tensor* t : {&ent_lab, &ent_row, &n_changed})
+    TORCH_CHECK(t->is_cuda() && t->dtype() == torch::kInt32 && t->is_contiguous());
+  for (const torch::Tensor* t : {&S, &cnt, &Q})
+    TORCH_CHECK(t->is_cuda() && t->dtype() == torch::kFloat64 && t->is_contiguous());
+  const int64_t n = X.size(0);
+  const int64_t k = R.size(0);
+  const int d = (int)X.size(1);
+  TORCH_CHECK(R.size(1) == d && S.dim() == 2 && S.size(0) == k && S.size(1) == d &&
+                  cnt.numel() == k && Q.numel() == k, "R, S, cnt and Q shapes disagree");
+  TORCH_CHECK(ent_lab.numel() == 2 * n && ent_row.numel() == 2 * n && n_changed.numel() == 1,
+              "entries do not belong to X");
+  TORCH_CHECK(m >= 0 && m <= n, "changed count out of range");
+  if (m == 0 || k == 0) return;
+  if (!sorted) {
+    const unsigned grid = (unsigned)std::min<int64_t>(2 * m, 8192);
+    hipLaunchKernelGGL(delta_direct_kernel, dim3(grid), dim3(256), 0, cur_stream(),
+                       X.data_ptr<float>(), ent_lab.data_ptr<int32_t>(),
+                       ent_row.data_ptr<int32_t>(), n_changed.data_ptr<int32_t>(), 2 * m,
+                       R.data_ptr<float>(), d, (int)k, S.data_ptr<double>(),
+                       cnt.data_ptr<double>(), Q.data_ptr<double>());
+    C10_HIP_KERNEL_LAUNCH_CHECK();
+    return;
+  }
+  // stable, so a segment keeps the list's order; labels outside [0, k) (there
+  // are none in a list built from two valid label vectors) fall outside every
+  // segment
+  auto sort = ent_lab.narrow(0, 0, 2 * m).sort(/*stable=*/true, /*dim=*/0, /*descending=*/false);
+  auto perm = std::get<1>(sort).contiguous();
+  auto sl = std::get<0>(sort).contiguous();
+  auto bounds = torch::arange(k + 1, ent_lab.options());
+  auto seg_off = torch::searchsorted(sl, bounds).contiguous();
+  // about 32 entries per block before a label is split further
+  const int nsplit = (int)std::clamp<int64_t>((2 * m) / (32 * k), 1, LA_SPLIT);
+  const bool aligned = ((uintptr_t)X.data_ptr() | (uintptr_t)R.data_ptr()) % 16 == 0;
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)(k * nsplit)), dim3(256), 0, cur_stream(),
+                       X.data_ptr<float>(), ent_row.data_ptr<int32_t>(),
+                       perm.data_ptr<int64_t>(), seg_off.data_ptr<int64_t>(),
+                       R.data_ptr<float>(), d, nsplit, S.data_ptr<double>(),
+                       cnt.data_ptr<double>(), Q.data_ptr<double>());
+  };
+  if (d % 4 == 0 && aligned) launch(delta_segment_kernel<true>);
+  else launch(delta_segment_kernel<false>);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+}
+
+// (out f64 [3] = inertia, drift, sum Q; sums f64 [k,d]) from the moments
+// about R and the centres C, as specified above kmeans_anchor_inertia_kernel.
+std::vector<torch::Tensor> kmeans_anchor_inertia(torch::Tensor C, torch::Tensor R,
+                                                 torch::Tensor S, torch::Tensor cnt,
+                                                 torch::Tensor Q, torch::Tensor E) {
+  for (const torch::Tensor* t : {&C, &R})
+    TORCH_CHECK(t->is_cuda() && t->dtype() == torch::kFloat32 && t->is_contiguous() &&
+                    t->dim() == 2);
+  for (const torch::Tensor* t : {&S, &cnt, &Q, &E})
+    TORCH_CHECK(t->is_cuda() && t->dtype() == torch::kFloat64 && t->is_contiguous());
+  const int64_t k = C.size(0);
+  const int d = (int)C.size(1);
+  TORCH_CHECK(R.size(0) == k && R.size(1) == d && S.dim() == 2 && S.size(0) == k &&
+                  S.size(1) == d && cnt.numel() == k && Q.numel() == k &&
+                  E.numel() == S.numel(),
+              "C, R, S, cnt, Q and E shapes disagree");
+  auto out = torch::zeros({3}, S.options());
+  auto sums = torch::empty({k, (int64_t)d}, S.options());
+  if (k > 0) {
+    hipLaunchKernelGGL(kmeans_anchor_inertia_kernel, dim3((unsigned)k), dim3(256), 0,
+                       cur_stream(), C.data_ptr<float>(), R.data_ptr<float>(),
+                       S.data_ptr<double>(), cnt.data_ptr<double>(), Q.data_ptr<double>(),
+                       E.data_ptr<double>(), d, sums.data_ptr<double>(),
+                       out.data_ptr<double>());
+    C10_HIP_KERNEL_LAUNCH_CHECK();
+  }
+  return {out, sums};
 }
 
 // (labels i32 [n], min_dists f64 [n], inertia f64 [1]) for f64 X, C and |x|^2.
@@ -7036,7 +7418,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "dynamic LDS of kmeans_step_resident for (k, d); 0 where the shape is not legal");
   m.def("label_accumulate", &label_accumulate, "per-center sum/count scatter");
   m.def("label_accumulate_inertia", &label_accumulate_inertia, "sorted per-center sum/count + sum (x - c)^2 in the same pass",
-        py::arg("X"), py::arg("labels"), py::arg("C"), py::arg("vec") = LA_VEC_DEFAULT);
+        py::arg("X"), py::arg("labels"), py::arg("C"), py::arg("vec") = LA_VEC_DEFAULT,
+        py::arg("anchor") = false);
+  m.def("kmeans_label_delta", &kmeans_label_delta,
+        "signed (label, row) entries of the rows whose label changed; brings prev up to date");
+  m.def("kmeans_delta_accumulate", &kmeans_delta_accumulate,
+        "applies the changed rows to the anchored per-centre moments, in place",
+        py::arg("X"), py::arg("ent_lab"), py::arg("ent_row"), py::arg("n_changed"),
+        py::arg("m"), py::arg("R"), py::arg("S"), py::arg("cnt"), py::arg("Q"),
+        py::arg("sorted") = true);
+  m.def("kmeans_anchor_inertia", &kmeans_anchor_inertia,
+        "(inertia, drift, sum Q) and the per-centre sums from the moments about the anchors");
   m.def("gram_f32", &gram_f32, "A^T A via MFMA f32");
   m.def("moments_f64", &moments_f64,
         "[X | 1 | y]^T [X | 1 | y] in f64 on f64 MFMA: Gram, column sums, X^T y and the y moments in one pass",

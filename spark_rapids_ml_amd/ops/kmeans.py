@@ -28,6 +28,18 @@ over X. A chunk with too many near-ties adds the other two terms onto the
 same dot block. That path reports the inertia `label_accumulate_inertia`
 sums beside the accumulation, as (x − c)² directly.
 
+The same cache entry carries the accumulation from step to step
+(`_accumulate_delta`, SRML_KMEANS_DELTA=0 disables it): a private copy of the
+last labels and, per centre, the count, Σ(x − r) and Σ|x − r|² about an anchor
+r, the centre at the last full pass. `kmeans_label_delta` lists the rows whose
+label changed, `kmeans_delta_accumulate` moves them between their centres'
+moments (X is read at those rows only) and `kmeans_anchor_inertia` evaluates
+sums and inertia for the current centres; 7.1 against 9.9 ms per step once few
+rows change (profiles/README.md "Delta step"). The full pass over X runs on a
+fresh entry or another k, when more than `F_DELTA` of the rows changed, and
+when the centres have drifted from their anchors by more than the rows lie
+around them.
+
 f64 rows (float32_inputs=False) have a path of their own, `_step_f64`:
 `kmeans_assign_f64` forms c² − 2x·c on mfma_f64_16x16x4f64 with the running
 (score, index) argmin in registers (lower index on an exact tie) and per-block
@@ -94,6 +106,9 @@ def kmeans_assign_reduce(
                     ext, X, C, x_sq, prep, exact=variant == "split_f64"
                 )
                 if inertia is None:
+                    if os.environ.get("SRML_KMEANS_DELTA") != "0":
+                        return (labels, *_accumulate_delta(ext, X, labels, C, prep))
+                    prep.k = 0  # the moments miss this step: not to be resumed
                     sums, counts, inertia = ext.label_accumulate_inertia(
                         X, labels, C.contiguous()
                     )
@@ -398,9 +413,17 @@ F_HI = 0.20
 
 class _Prepared:
     """What a fit reuses of X: the centring point, the bf16 hi plane of X - mu
-    ([n, dp], zero pad columns) and |x - mu|², plus the key they belong to."""
+    ([n, dp], zero pad columns) and |x - mu|², plus the key they belong to.
 
-    __slots__ = ("ref", "key", "mu", "H", "a_sq", "finalizer")
+    And what `_accumulate_delta` carries from step to step, valid while
+    `k` != 0: `prev`, a private copy of the last labels; the anchors `R`
+    (f32 [k, d], the centres of the last full pass); and the per-centre
+    moments about them in f64, `cnt` [k], `S` = Σ(x − r) [k, d] and
+    `Q` = Σ|x − r|² [k]; `E` [k, d] is what the f32 Σx of that full pass
+    differed from S + cnt·R by. They depend on the labels alone, never on C."""
+
+    __slots__ = ("ref", "key", "mu", "H", "a_sq", "finalizer",
+                 "k", "prev", "R", "S", "cnt", "Q", "E")
 
 
 _PREP: Optional[_Prepared] = None
@@ -455,8 +478,70 @@ def _prepared(ext, X: torch.Tensor, C: torch.Tensor) -> Optional[_Prepared]:
     p.ref = weakref.ref(X)
     p.key = _key(X)
     p.finalizer = weakref.finalize(X, _drop_prepared, p)
+    p.k = 0
+    p.prev = p.R = p.S = p.cnt = p.Q = p.E = None
     _PREP = p
     return p
+
+
+# Share of the rows that may change label before a step takes the full pass
+# instead of the delta (see `_accumulate_delta`). Measured at 1M x 3000, k=1000
+# (tools/time_kmeans_delta.py; table in profiles/README.md "Delta step"): the
+# delta path takes 0.40 ms at 1 % changed, 1.04 at 10 %, 1.89 at 25 % and 3.30
+# at 50 % against 2.9 ms for the full pass; they cross near 40 %.
+F_DELTA = 0.25
+# Form of `kmeans_delta_accumulate`: entries sorted by label and streamed per
+# segment, or one block per entry with an f64 atomic per column (faster only
+# below 0.5 % changed, by 0.08 ms; 3.6 against 1.0 ms at 10 %).
+DELTA_SORTED = True
+
+
+def _accumulate_delta(
+    ext, X: torch.Tensor, labels: torch.Tensor, C: torch.Tensor, prep: _Prepared
+) -> Tuple[torch.Tensor, torch.Tensor, float]:
+    """(sums f64 [k,d], counts f64 [k], inertia) of `labels`, from the rows
+    that changed label since the last call on this entry where it can.
+
+    The entry keeps n_j, S_j = Σ(x − r_j) and Q_j = Σ|x − r_j|² per centre
+    about the anchors r_j, the centres of the last full pass. Then
+    Σx = S_j + n_j r_j and Σ|x − c_j|² = Q_j − 2(c_j − r_j)·S_j + n_j|c_j − r_j|²
+    (`kmeans_anchor_inertia`), and a row that moves from one label to another
+    leaves the one and enters the other as a direct difference against their
+    anchors (`kmeans_label_delta`, `kmeans_delta_accumulate`): X is read at
+    the changed rows only. Full pass (`label_accumulate_inertia` with
+    `anchor`, which also re-anchors at C) when the entry holds no moments for
+    this k, when more than F_DELTA of the rows changed, and when the drift
+    D = Σ n_j|c_j − r_j|² exceeds ΣQ_j, the correction terms then being no
+    longer small beside what they correct. What is returned never aliases
+    the kept state, nor the state the caller's labels."""
+    n, k = X.shape[0], C.shape[0]
+    Cc = C.contiguous()
+    if prep.k == k:
+        ent_lab, ent_row, n_changed = ext.kmeans_label_delta(labels, prep.prev)
+        m = int(n_changed.item())
+        if m <= F_DELTA * n:
+            if m:
+                ext.kmeans_delta_accumulate(
+                    X, ent_lab, ent_row, n_changed, m, prep.R, prep.S, prep.cnt, prep.Q,
+                    DELTA_SORTED,
+                )
+            out, sums = ext.kmeans_anchor_inertia(
+                Cc, prep.R, prep.S, prep.cnt, prep.Q, prep.E
+            )
+            inertia, drift, q_sum = out.tolist()
+            if not drift > q_sum:
+                return sums, prep.cnt.clone(), inertia
+    sums, counts, inertia, Q, dsums = ext.label_accumulate_inertia(
+        X, labels, Cc, anchor=True
+    )
+    sums = sums.to(torch.float64)
+    prep.prev = labels.clone()
+    prep.R = Cc.clone()
+    prep.S, prep.cnt, prep.Q, prep.k = dsums.to(torch.float64), counts.to(torch.float64), Q, k
+    # S is kept about R so that Σ(x − r) does not carry the f32 rounding of Σx
+    # far from the origin; E ties the sums returned from now on to this Σx
+    prep.E = sums - torch.addcmul(prep.S, prep.cnt[:, None], Cc.to(torch.float64))
+    return sums, prep.cnt.clone(), float(inertia.item())
 
 
 def _assign_prepared(
