@@ -3054,7 +3054,8 @@ __global__ __launch_bounds__(256) void kmeans_argmin_kn_screen_kernel(
     float* __restrict__ min_d,        // [m]
     double* __restrict__ inertia,     // [1] accumulated
     int32_t* __restrict__ flagged_rows,  // [m]
-    int32_t* __restrict__ n_flagged) {   // [1] accumulated
+    int32_t* __restrict__ n_flagged,     // [1] accumulated
+    float* __restrict__ gap_out) {       // [m] or null: second - best - margin, 0 if flagged
   extern __shared__ float csq_s[];
   for (int e = threadIdx.x; e < k; e += 256) csq_s[e] = c_sq[e];
   __syncthreads();
@@ -3098,6 +3099,11 @@ __global__ __launch_bounds__(256) void kmeans_argmin_kn_screen_kernel(
     }
     const float asq = valid ? a_sq[i] : 0.0f;
     const bool flag = valid && second <= best + ms * sqrtf(asq);
+    if (gap_out != nullptr && valid) {
+      // each step rounded on its own (no fma), so a host model reproduces it
+      const float g = __fsub_rn(__fsub_rn(second, best), __fmul_rn(ms, sqrtf(asq)));
+      gap_out[i] = flag ? 0.0f : fmaxf(g, 0.0f);
+    }
     if (valid && !flag) {
       const float d2 = fmaxf(best + asq, 0.0f);
       labels[i] = bi;
@@ -3122,6 +3128,190 @@ __global__ __launch_bounds__(256) void kmeans_argmin_kn_screen_kernel(
     __syncthreads();
   }
   if (threadIdx.x == 0) atomicAdd(inertia, red_s[0]);
+}
+
+// ---------------------------------------------------------------------------
+// Row bounds (ops/kmeans.py `_assign_bounded`). A reference pass keeps, per
+// row, its label a and a certified lower bound g of (second - best) of
+//   v_j = |c'_j|^2 - 2 x'.c'_j,   x' = f32(x - mu), c'_j = f32(c_j - mu),
+// at the reference centres. When the centres move from c_ref to c (same mu),
+//   v_j(c) - v_j(c_ref) = D_j - 2 x'.(c'_j - c'_ref,j),
+//   D_j = |c'_j|^2 - |c'_ref,j|^2,  |x'.(c'_j - c'_ref,j)| <= r d_j,
+//   r = |x'|,  d_j = |c'_j - c'_ref,j|,
+// so v_a rises by at most D_a + 2 r d_a and every other v_j falls by at most
+// -(D_j - 2 r d_j): while
+//   g > (D_a + 2 r d_a) - min_{j != a}(D_j - 2 r d_j)
+// label a is still the strict argmin (Hamerly's bound on the score v).
+//
+// kmeans_centre_drift: one block per centre; D_j and d_j^2 summed in f64 over
+// the f32-centred coordinates (D_j as sum (c' - c'_ref)(c' + c'_ref), free of
+// the cancellation of two large squares), d_j rounded up to f32, D_j to
+// nearest. Both are exact on integer-valued centres and mu.
+// ---------------------------------------------------------------------------
+
+__device__ __forceinline__ float f32_round_up(double v) {
+  float f = (float)v;
+  if ((double)f < v) f = __uint_as_float(__float_as_uint(f) + 1u);  // v >= 0 here
+  return f;
+}
+
+__global__ __launch_bounds__(256) void kmeans_centre_drift_kernel(
+    const float* __restrict__ C,      // [k, d]
+    const float* __restrict__ C_ref,  // [k, d]
+    const float* __restrict__ mu,     // [d]
+    int k, int d,
+    float* __restrict__ Delta,        // [k]  |c'|^2 - |c'_ref|^2
+    float* __restrict__ delta) {      // [k]  |c' - c'_ref|, rounded up
+  const int j = blockIdx.x;
+  const float* cr = C + (int64_t)j * d;
+  const float* rr = C_ref + (int64_t)j * d;
+  double sD = 0.0, sd = 0.0;
+  for (int e = threadIdx.x; e < d; e += 256) {
+    const float m = mu[e];
+    const double a = (double)(cr[e] - m), b = (double)(rr[e] - m);
+    sD = fma(a - b, a + b, sD);
+    sd = fma(a - b, a - b, sd);
+  }
+  __shared__ double red_D[256], red_d[256];
+  red_D[threadIdx.x] = sD;
+  red_d[threadIdx.x] = sd;
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) {
+    if (threadIdx.x < off) {
+      red_D[threadIdx.x] += red_D[threadIdx.x + off];
+      red_d[threadIdx.x] += red_d[threadIdx.x + off];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    Delta[j] = (float)red_D[0];
+    delta[j] = f32_round_up(sqrt(red_d[0]));
+  }
+}
+
+// ---------------------------------------------------------------------------
+// kmeans_bound_test: one thread per row, (D_j, d_j) staged in LDS a tile of
+// BOUND_TILE centres at a time and walked in batches as the screen walks its
+// dots. Row i with a = lab_ref[i], g = gap_ref[i], r = sqrt(a_sq[i]) passes iff
+//   g > 0  and  g > (D_a + 2 r d_a) - min_{j != a}(D_j - 2 r d_j) + slack,
+//   slack = slack_rel * (Dmax + 2 r dmax) + 2^-21 g,
+//   Dmax = max_j |D_j|, dmax = max_j d_j.
+// What slack has to cover, relative to (Dmax + 2 r dmax), which bounds each
+// of the two bracketed terms: a_sq is an f32 sum of d squares, its relative
+// error at most (d/64 + 8) 2^-24, half of that in r and so, r entering both
+// terms, 2 (d/64 + 8) 2^-25 in all: below 2^-12 for d <= 2^18; D_j to
+// nearest, 2^-24 each, the f64 sums behind D_j and d_j far below that;
+// sqrtf, the products and the sums of this expression, under ten roundings
+// of 2^-24 each: below 2^-20. slack_rel = 2^-10 (ops/kmeans.py) leaves a
+// factor of three on top. g itself is the f32 difference of three terms
+// (kmeans_argmin_kn_screen), within 2^-22 g of the certified value: 2^-21 g.
+// With no drift the right-hand side is 2^-21 g and every g > 0 passes. The
+// comparison is strict, so a tie never passes. A row that fails is appended
+// to `active` (one ballot and one atomic per wave, as the screen does).
+// ---------------------------------------------------------------------------
+
+constexpr int BOUND_TILE = 4096;
+
+__global__ __launch_bounds__(256) void kmeans_bound_test_kernel(
+    const float* __restrict__ gap_ref,   // [n]
+    const int32_t* __restrict__ lab_ref, // [n]
+    const float* __restrict__ a_sq,      // [n]
+    const float* __restrict__ Delta,     // [k]
+    const float* __restrict__ delta,     // [k]
+    float slack_rel, int64_t n, int k,
+    int32_t* __restrict__ active,        // [n]
+    int32_t* __restrict__ n_active) {    // [1] accumulated
+  __shared__ float D_s[BOUND_TILE], d_s[BOUND_TILE];
+  __shared__ float red_s[2][4];
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  // Dmax, dmax: every block reduces the k pairs itself (k <= 16384)
+  float Dm = 0.0f, dm = 0.0f;
+  for (int e = threadIdx.x; e < k; e += 256) {
+    Dm = fmaxf(Dm, fabsf(Delta[e]));
+    dm = fmaxf(dm, delta[e]);
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    Dm = fmaxf(Dm, __shfl_xor(Dm, off, 64));
+    dm = fmaxf(dm, __shfl_xor(dm, off, 64));
+  }
+  if (lane == 0) { red_s[0][wave] = Dm; red_s[1][wave] = dm; }
+  __syncthreads();
+  Dm = fmaxf(fmaxf(red_s[0][0], red_s[0][1]), fmaxf(red_s[0][2], red_s[0][3]));
+  dm = fmaxf(fmaxf(red_s[1][0], red_s[1][1]), fmaxf(red_s[1][2], red_s[1][3]));
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  // i0 is block-uniform so every lane reaches the barriers and the ballot
+  for (int64_t i0 = (int64_t)blockIdx.x * 256; i0 < n; i0 += stride) {
+    const int64_t i = i0 + threadIdx.x;
+    const bool valid = i < n;
+    const float g = valid ? gap_ref[i] : 0.0f;
+    const int a = valid ? lab_ref[i] : 0;
+    const float r2 = 2.0f * sqrtf(valid ? a_sq[i] : 0.0f);
+    float lo = 3.0e38f, up = 3.0e38f;  // up stays there if a is no centre: the row fails
+    for (int t0 = 0; t0 < k; t0 += BOUND_TILE) {
+      const int tk = min(BOUND_TILE, k - t0);
+      __syncthreads();  // the tile of the last round has been read
+      for (int e = threadIdx.x; e < tk; e += 256) {
+        D_s[e] = Delta[t0 + e];
+        d_s[e] = delta[t0 + e];
+      }
+      __syncthreads();
+      int jj = 0;
+      for (; jj + SCREEN_BATCH <= tk; jj += SCREEN_BATCH) {
+#pragma unroll
+        for (int u = 0; u < SCREEN_BATCH; ++u) {
+          const float rd = r2 * d_s[jj + u];
+          const bool own = t0 + jj + u == a;
+          up = own ? D_s[jj + u] + rd : up;
+          lo = own ? lo : fminf(lo, D_s[jj + u] - rd);
+        }
+      }
+      for (; jj < tk; ++jj) {
+        const float rd = r2 * d_s[jj];
+        const bool own = t0 + jj == a;
+        up = own ? D_s[jj] + rd : up;
+        lo = own ? lo : fminf(lo, D_s[jj] - rd);
+      }
+    }
+    const float slack = slack_rel * (Dm + r2 * dm) + 0x1p-21f * g;
+    const bool pass = g > 0.0f && g > (up - lo) + slack;
+    const bool flag = valid && !pass;
+    const unsigned long long mask = __ballot(flag);
+    if (mask != 0ull) {
+      const int leader = __ffsll((long long)mask) - 1;
+      int base = 0;
+      if (lane == leader) base = atomicAdd(n_active, __popcll(mask));
+      base = __shfl(base, leader, 64);
+      if (flag)
+        active[base + __popcll(mask & ((1ull << lane) - 1ull))] = (int32_t)i;
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// kmeans_gather_rows_bf16: out[f] = H[rows[f]] for the first m listed rows of
+// the hi plane, one wave per row, 16-byte loads and stores (dp is a multiple
+// of 32, so every row of H and of out starts 16-byte aligned). A row id
+// outside [0, n) leaves zeros.
+// ---------------------------------------------------------------------------
+
+__global__ __launch_bounds__(256) void kmeans_gather_rows_bf16_kernel(
+    const uint16_t* __restrict__ H,    // [n, dp] bf16 bits
+    const int32_t* __restrict__ rows,  // [>= m]
+    int64_t n, int64_t m, int dp,
+    uint16_t* __restrict__ out) {      // [m, dp]
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int groups = dp >> 3;
+  const int64_t wstride = (int64_t)gridDim.x * 4;
+  for (int64_t f = (int64_t)blockIdx.x * 4 + wave; f < m; f += wstride) {
+    const int64_t r = rows[f];
+    const bool ok = r >= 0 && r < n;
+    const uint4* src = reinterpret_cast<const uint4*>(H + (ok ? r : 0) * (int64_t)dp);
+    uint4* dst = reinterpret_cast<uint4*>(out + f * (int64_t)dp);
+    for (int g = lane; g < groups; g += 64) dst[g] = ok ? src[g] : make_uint4(0u, 0u, 0u, 0u);
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -6558,9 +6748,12 @@ std::vector<torch::Tensor> kmeans_split_bf16_hi(torch::Tensor A, torch::Tensor m
   return kmeans_split_impl<false>(A, mu);
 }
 
+// `gap_out` (keyword, optional): f32 [m] that receives second - best - margin
+// per row, 0 for a flagged row; the five results are the same with and without.
 std::vector<torch::Tensor> kmeans_argmin_kn_screen(torch::Tensor dots, torch::Tensor a_sq,
                                                    torch::Tensor c_sq,
-                                                   torch::Tensor margin_scale) {
+                                                   torch::Tensor margin_scale,
+                                                   c10::optional<torch::Tensor> gap_out) {
   TORCH_CHECK(dots.is_cuda() && dots.dtype() == torch::kFloat32 && dots.is_contiguous());
   TORCH_CHECK(a_sq.is_cuda() && a_sq.dtype() == torch::kFloat32 && a_sq.is_contiguous());
   TORCH_CHECK(c_sq.is_cuda() && c_sq.dtype() == torch::kFloat32 && c_sq.is_contiguous());
@@ -6571,6 +6764,14 @@ std::vector<torch::Tensor> kmeans_argmin_kn_screen(torch::Tensor dots, torch::Te
   TORCH_CHECK(a_sq.numel() == m && c_sq.numel() == k, "a_sq / c_sq do not match dots");
   TORCH_CHECK((size_t)k * 4 <= 64 * 1024, "k too large for LDS stage");
   TORCH_CHECK(m < (int64_t)1 << 31, "row chunk too large for int32 row ids");
+  float* gap_p = nullptr;
+  if (gap_out.has_value()) {
+    const torch::Tensor& g = *gap_out;
+    TORCH_CHECK(g.is_cuda() && g.dtype() == torch::kFloat32 && g.is_contiguous() &&
+                    g.numel() == m,
+                "gap_out must be a contiguous f32 device vector with one entry per row");
+    gap_p = g.data_ptr<float>();
+  }
   auto iopt = dots.options().dtype(torch::kInt32);
   auto labels = torch::empty({m}, iopt);
   auto min_d = torch::empty({m}, dots.options());
@@ -6584,10 +6785,84 @@ std::vector<torch::Tensor> kmeans_argmin_kn_screen(torch::Tensor dots, torch::Te
                        a_sq.data_ptr<float>(), c_sq.data_ptr<float>(),
                        margin_scale.data_ptr<float>(), m, k, labels.data_ptr<int32_t>(),
                        min_d.data_ptr<float>(), inertia.data_ptr<double>(),
-                       flagged.data_ptr<int32_t>(), n_flagged.data_ptr<int32_t>());
+                       flagged.data_ptr<int32_t>(), n_flagged.data_ptr<int32_t>(), gap_p);
     C10_HIP_KERNEL_LAUNCH_CHECK();
   }
   return {labels, min_d, inertia, flagged, n_flagged};
+}
+
+// (Delta f32 [k], delta f32 [k]) of the centres C against C_ref, both centred
+// by mu, as specified above kmeans_centre_drift_kernel.
+std::vector<torch::Tensor> kmeans_centre_drift(torch::Tensor C, torch::Tensor C_ref,
+                                               torch::Tensor mu) {
+  for (const torch::Tensor* t : {&C, &C_ref, &mu})
+    TORCH_CHECK(t->is_cuda() && t->dtype() == torch::kFloat32 && t->is_contiguous(),
+                "kmeans_centre_drift takes contiguous f32 device tensors");
+  TORCH_CHECK(C.dim() == 2 && C_ref.sizes() == C.sizes() && mu.numel() == C.size(1),
+              "C, C_ref and mu shapes disagree");
+  const int k = (int)C.size(0);
+  const int d = (int)C.size(1);
+  auto Delta = torch::empty({(int64_t)k}, C.options());
+  auto delta = torch::empty({(int64_t)k}, C.options());
+  if (k > 0) {
+    hipLaunchKernelGGL(kmeans_centre_drift_kernel, dim3((unsigned)k), dim3(256), 0,
+                       cur_stream(), C.data_ptr<float>(), C_ref.data_ptr<float>(),
+                       mu.data_ptr<float>(), k, d, Delta.data_ptr<float>(),
+                       delta.data_ptr<float>());
+    C10_HIP_KERNEL_LAUNCH_CHECK();
+  }
+  return {Delta, delta};
+}
+
+// (active i32 [n], n_active i32 [1]): the rows whose kept label is not
+// certified against the drift, as specified above kmeans_bound_test_kernel.
+std::vector<torch::Tensor> kmeans_bound_test(torch::Tensor gap_ref, torch::Tensor lab_ref,
+                                             torch::Tensor a_sq, torch::Tensor Delta,
+                                             torch::Tensor delta, double slack_rel) {
+  for (const torch::Tensor* t : {&gap_ref, &a_sq, &Delta, &delta})
+    TORCH_CHECK(t->is_cuda() && t->dtype() == torch::kFloat32 && t->is_contiguous() &&
+                    t->dim() == 1,
+                "kmeans_bound_test takes contiguous f32 device vectors");
+  TORCH_CHECK(lab_ref.is_cuda() && lab_ref.dtype() == torch::kInt32 && lab_ref.is_contiguous());
+  const int64_t n = gap_ref.numel();
+  const int64_t k = Delta.numel();
+  TORCH_CHECK(lab_ref.numel() == n && a_sq.numel() == n && delta.numel() == k,
+              "per-row / per-centre sizes disagree");
+  TORCH_CHECK(n < (int64_t)1 << 31, "too many rows for int32 row ids");
+  TORCH_CHECK(k >= 1 && k <= 16384, "kmeans_bound_test: k out of range");
+  auto active = torch::empty({n}, lab_ref.options());
+  auto n_active = torch::zeros({1}, lab_ref.options());
+  if (n > 0) {
+    const unsigned grid = (unsigned)std::min<int64_t>(4096, (n + 255) / 256);
+    hipLaunchKernelGGL(kmeans_bound_test_kernel, dim3(grid), dim3(256), 0, cur_stream(),
+                       gap_ref.data_ptr<float>(), lab_ref.data_ptr<int32_t>(),
+                       a_sq.data_ptr<float>(), Delta.data_ptr<float>(),
+                       delta.data_ptr<float>(), (float)slack_rel, n, (int)k,
+                       active.data_ptr<int32_t>(), n_active.data_ptr<int32_t>());
+    C10_HIP_KERNEL_LAUNCH_CHECK();
+  }
+  return {active, n_active};
+}
+
+// out bf16 [m, dp] = H[rows[:m]]; `m` is the count the host has read.
+torch::Tensor kmeans_gather_rows_bf16(torch::Tensor H, torch::Tensor rows, int64_t m) {
+  TORCH_CHECK(H.is_cuda() && H.dtype() == torch::kBFloat16 && H.is_contiguous() &&
+                  H.dim() == 2 && H.size(1) % 32 == 0,
+              "H must be a contiguous bf16 [n, dp] device plane, dp a multiple of 32");
+  TORCH_CHECK(rows.is_cuda() && rows.dtype() == torch::kInt32 && rows.is_contiguous());
+  TORCH_CHECK(m >= 0 && m <= rows.numel(), "m exceeds the row list");
+  const int64_t n = H.size(0);
+  const int dp = (int)H.size(1);
+  auto out = torch::empty({m, (int64_t)dp}, H.options());
+  if (m > 0) {
+    const unsigned grid = (unsigned)std::min<int64_t>(1 << 20, (m + 3) / 4);
+    hipLaunchKernelGGL(kmeans_gather_rows_bf16_kernel, dim3(grid), dim3(256), 0, cur_stream(),
+                       reinterpret_cast<const uint16_t*>(H.data_ptr()),
+                       rows.data_ptr<int32_t>(), n, m, dp,
+                       reinterpret_cast<uint16_t*>(out.data_ptr()));
+    C10_HIP_KERNEL_LAUNCH_CHECK();
+  }
+  return out;
 }
 
 void kmeans_refine(torch::Tensor X, torch::Tensor C, torch::Tensor dots,
@@ -7410,7 +7685,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("kmeans_argmin_nk", &kmeans_argmin_nk, "argmin epilogue over a row-major [m,k] GEMM dot block");
   m.def("kmeans_split_bf16", &kmeans_split_bf16, "centre + split f32 rows into bf16 hi|lo halves, with |x'|^2");
   m.def("kmeans_split_bf16_hi", &kmeans_split_bf16_hi, "centre + round f32 rows to their bf16 hi plane, with |x'|^2");
-  m.def("kmeans_argmin_kn_screen", &kmeans_argmin_kn_screen, "best/second argmin over a screened [k,n] dot block; flags near-ties");
+  m.def("kmeans_argmin_kn_screen", &kmeans_argmin_kn_screen, "best/second argmin over a screened [k,n] dot block; flags near-ties",
+        py::arg("dots"), py::arg("a_sq"), py::arg("c_sq"), py::arg("margin_scale"),
+        py::kw_only(), py::arg("gap_out") = py::none());
+  m.def("kmeans_centre_drift", &kmeans_centre_drift,
+        "per centre |c'|^2 - |c'_ref|^2 and |c' - c'_ref| (rounded up) against reference centres");
+  m.def("kmeans_bound_test", &kmeans_bound_test,
+        "lists the rows whose kept label the drift bound does not certify");
+  m.def("kmeans_gather_rows_bf16", &kmeans_gather_rows_bf16,
+        "gathers listed rows of the bf16 hi plane into a contiguous block");
   m.def("kmeans_refine", &kmeans_refine, "exact f64 decision for the flagged rows");
   m.def("kmeans_step_resident", &kmeans_step_resident,
         "one-pass Lloyd step (labels, sums, counts, inertia) with the centres resident in LDS");

@@ -40,6 +40,14 @@ fresh entry or another k, when more than `F_DELTA` of the rows changed, and
 when the centres have drifted from their anchors by more than the rows lie
 around them.
 
+It also carries the assignment (`_assign_bounded`, SRML_KMEANS_BOUNDS=0
+disables it): the centres, labels and certified per-row gaps of the last pass
+that screened every row. `kmeans_centre_drift` and `kmeans_bound_test` keep
+the label of every row whose gap exceeds what the centres' drift since can
+have changed; the others are gathered (`kmeans_gather_rows_bf16`) and take the
+GEMM and the screen on their own; 2.8 against 7.1 ms per step
+(profiles/README.md "Row bounds").
+
 f64 rows (float32_inputs=False) have a path of their own, `_step_f64`:
 `kmeans_assign_f64` forms c² − 2x·c on mfma_f64_16x16x4f64 with the running
 (score, index) argmin in registers (lower index on an exact tie) and per-block
@@ -420,10 +428,19 @@ class _Prepared:
     (f32 [k, d], the centres of the last full pass); and the per-centre
     moments about them in f64, `cnt` [k], `S` = Σ(x − r) [k, d] and
     `Q` = Σ|x − r|² [k]; `E` [k, d] is what the f32 Σx of that full pass
-    differed from S + cnt·R by. They depend on the labels alone, never on C."""
+    differed from S + cnt·R by. They depend on the labels alone, never on C.
+
+    And the reference state of the row bounds (`_assign_bounded`), valid while
+    `ref_k` != 0: `C_ref`, a private copy of the centres of the last reference
+    pass; `lab_ref` (i32 [n]), its final labels; and `gap_ref` (f32 [n]), per
+    row a certified lower bound of (second − best) of |c'_j|² − 2x'·c'_j at
+    those centres, 0 where the row was a near-tie. `changed` is the number of
+    rows whose label changed at the last step, as `_accumulate_delta` read it
+    (n where it did not, 0 on an entry it has not seen)."""
 
     __slots__ = ("ref", "key", "mu", "H", "a_sq", "finalizer",
-                 "k", "prev", "R", "S", "cnt", "Q", "E")
+                 "k", "prev", "R", "S", "cnt", "Q", "E",
+                 "ref_k", "C_ref", "lab_ref", "gap_ref", "changed")
 
 
 _PREP: Optional[_Prepared] = None
@@ -480,6 +497,8 @@ def _prepared(ext, X: torch.Tensor, C: torch.Tensor) -> Optional[_Prepared]:
     p.finalizer = weakref.finalize(X, _drop_prepared, p)
     p.k = 0
     p.prev = p.R = p.S = p.cnt = p.Q = p.E = None
+    p.ref_k = p.changed = 0
+    p.C_ref = p.lab_ref = p.gap_ref = None
     _PREP = p
     return p
 
@@ -516,9 +535,10 @@ def _accumulate_delta(
     the kept state, nor the state the caller's labels."""
     n, k = X.shape[0], C.shape[0]
     Cc = C.contiguous()
+    prep.changed = n  # not known on a fresh entry or another k
     if prep.k == k:
         ent_lab, ent_row, n_changed = ext.kmeans_label_delta(labels, prep.prev)
-        m = int(n_changed.item())
+        m = prep.changed = int(n_changed.item())
         if m <= F_DELTA * n:
             if m:
                 ext.kmeans_delta_accumulate(
@@ -544,6 +564,73 @@ def _accumulate_delta(
     return sums, prep.cnt.clone(), float(inertia.item())
 
 
+# Row bounds (see `_assign_bounded`). BOUND_SLACK is `slack_rel` of
+# `kmeans_bound_test`, derived above that kernel (hip/ops.hip).
+BOUND_SLACK = 2.0 ** -10
+# Share of the rows the bound test may leave active before the step is a
+# reference pass instead. Measured at 1M x 3000, k=1000
+# (tools/time_kmeans_bounds.py; table in profiles/README.md "Row bounds"):
+# the active path takes 1.47 ms with the 1 % near-ties alone, 1.91 at 5 % more,
+# 2.30 at 10 %, 3.54 at 25 % and 5.54 at 50 % against 6.8 ms for the full
+# screen. They would cross past 60 %; the cut-off stays at its starting value,
+# a step over it being one whose centres still move, where a new reference is
+# worth more than the step saved.
+F_SKIP = 0.25
+# The bound test is tried only if at most this share of the rows changed
+# label at the last step. A test that fails costs 0.4 to 0.6 ms on top of the
+# reference pass that follows (`kmeans_bound_test` alone 0.50 ms); in the same
+# course it failed after every step that changed 0.26 % of the labels or more
+# (576k rows active after that one) and passed after 0.02 % (132k active).
+F_TRY = 0.001
+
+
+def _assign_bounded(
+    ext, X: torch.Tensor, Cc: torch.Tensor, x_sq: torch.Tensor, prep: _Prepared,
+    Ch: torch.Tensor, c_sq: torch.Tensor, margin_hi: torch.Tensor, exact: bool,
+) -> Optional[torch.Tensor]:
+    """Labels of this step from the reference state of the entry, or None if
+    more than F_SKIP of the rows need their scores (a reference pass follows).
+
+    With v_j = |c'_j|² − 2x'·c'_j, a move of the centres from C_ref to C
+    raises v_a by at most Δ_a + 2rδ_a and lowers any other v_j by at most
+    −(Δ_j − 2rδ_j) (Δ_j = |c'_j|² − |c'_ref,j|², δ_j = |c_j − c_ref,j|,
+    r = |x'|: `kmeans_centre_drift`). A row whose certified gap at C_ref
+    exceeds the sum of the two (`kmeans_bound_test`) still has its reference
+    label as strict argmin and needs no dot product. The other, active rows
+    take today's path on their own: their rows of the hi plane gathered
+    (`kmeans_gather_rows_bf16`), the hi·hi GEMM, the screen, and its near-ties
+    decided as `_assign_prepared` decides them. The reference state is not
+    rewritten, so every step is tested against the same reference, and the
+    returned labels never alias it."""
+    n = X.shape[0]
+    Delta, delta = ext.kmeans_centre_drift(Cc, prep.C_ref, prep.mu)
+    active, n_active = ext.kmeans_bound_test(
+        prep.gap_ref, prep.lab_ref, prep.a_sq, Delta, delta, BOUND_SLACK
+    )
+    m = int(n_active.item())
+    if m > F_SKIP * n:
+        return None
+    labels = prep.lab_ref.clone()
+    if m == 0:
+        return labels
+    rows = active[:m].long()
+    Hg = ext.kmeans_gather_rows_bf16(prep.H, active, m)
+    dots = torch.mm(Ch, Hg.T, out_dtype=torch.float32)
+    a_sq = prep.a_sq[rows]
+    lb, md, it, flagged, n_flagged = ext.kmeans_argmin_kn_screen(dots, a_sq, c_sq, margin_hi)
+    nf = int(n_flagged.item())
+    if nf and exact:
+        ext.kmeans_refine(
+            X[rows], Cc, dots, c_sq, a_sq, margin_hi, flagged, n_flagged, lb, md, it
+        )
+    elif nf:
+        near = flagged[:nf].long()
+        lf, _itf = _refine_f32(ext, X, Cc, x_sq, rows[near])
+        lb[near] = lf
+    labels[rows] = lb
+    return labels
+
+
 def _assign_prepared(
     ext, X: torch.Tensor, C: torch.Tensor, x_sq: torch.Tensor, prep: _Prepared,
     max_dots_bytes: int = 8 << 30, exact: bool = False,
@@ -559,7 +646,13 @@ def _assign_prepared(
     up — it is split in full against the same mu, `addmm` adds hi·lo + lo·hi
     onto the same dot block, and it goes on exactly as `_assign_split` does
     from its screen, F_MAX and `_fallback_f32` included; then the cache is
-    dropped and the result is (labels, inertia) of the f32 path."""
+    dropped and the result is (labels, inertia) of the f32 path.
+
+    Unless SRML_KMEANS_BOUNDS=0, a pass that screens every row is also the
+    reference pass of the row bounds: it leaves `C_ref`, `lab_ref` and
+    `gap_ref` on the entry (the screen's gap output; a chunk that fell up
+    keeps the gap of its three-term screen), and while the entry holds them
+    for this k, `_assign_bounded` is asked first."""
     n, k = X.shape[0], C.shape[0]
     Cc = C.contiguous()
     mu, H = prep.mu, prep.H
@@ -569,6 +662,14 @@ def _assign_prepared(
     ClCh = None
     c_max = c_sq.max().sqrt()
     margin_hi = ((4.0 * EPS_HI) * c_max).reshape(1)
+
+    bounds = os.environ.get("SRML_KMEANS_BOUNDS") != "0"
+    if bounds and prep.ref_k == k and prep.changed <= F_TRY * n:
+        labels = _assign_bounded(ext, X, Cc, x_sq, prep, Ch, c_sq, margin_hi, exact)
+        if labels is not None:
+            return labels, None
+    prep.ref_k = 0  # rewritten below, or stale
+    gap = torch.empty(n, dtype=torch.float32, device=X.device) if bounds else None
 
     rchunk = max(256, int(max_dots_bytes // (k * 4)))
     single = rchunk >= n
@@ -582,8 +683,9 @@ def _assign_prepared(
             dots = torch.empty((k, e - s), dtype=torch.float32, device=X.device)
         torch.mm(Ch, H[s:e].T, out_dtype=torch.float32, out=dots)
         margin = margin_hi
+        gap_kw = {"gap_out": gap[s:e]} if bounds else {}
         lb, md, it, flagged, n_flagged = ext.kmeans_argmin_kn_screen(
-            dots, a_sq, c_sq, margin
+            dots, a_sq, c_sq, margin, **gap_kw
         )
         nf = int(n_flagged.item())
         if nf > F_HI * (e - s):
@@ -595,7 +697,7 @@ def _assign_prepared(
             del SX
             margin = ((4.0 * SPLIT_EPS) * c_max).reshape(1)
             lb, md, it, flagged, n_flagged = ext.kmeans_argmin_kn_screen(
-                dots, a_sq, c_sq, margin
+                dots, a_sq, c_sq, margin, **gap_kw
             )
             nf = int(n_flagged.item())
             if nf > F_MAX * (e - s):
@@ -610,8 +712,11 @@ def _assign_prepared(
             lf, _itf = _refine_f32(ext, Xc, Cc, x_sq[s:e], rows)
             lb[rows] = lf
         if single:
-            return lb, None
-        labels[s:e] = lb
+            labels = lb
+        else:
+            labels[s:e] = lb
+    if bounds:
+        prep.C_ref, prep.lab_ref, prep.gap_ref, prep.ref_k = Cc.clone(), labels.clone(), gap, k
     return labels, None
 
 

@@ -46,8 +46,8 @@ class Ext:
         return getattr(real, name)
 
     @staticmethod
-    def kmeans_argmin_kn_screen(*a):
-        out = real.kmeans_argmin_kn_screen(*a)
+    def kmeans_argmin_kn_screen(*a, **kw):
+        out = real.kmeans_argmin_kn_screen(*a, **kw)
         flag_counts.append(out[4])
         return out
 
